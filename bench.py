@@ -20,6 +20,11 @@ with the exchange INSIDE the step (the inverse runs in >= 4 chunks, each chunk's
 next chunk's inverse) and reported next to it (`with_allgather`); for cfg5 the all-reduce of the moments is part of the
 algorithm and always inside the step.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line.  `--full` adds the side measurements to it: the
+`also` block (default workload, N = 1), the PCIe-inclusive rate and the CPU baseline (N = 1; `--no-also` / `--no-cpu` drop
+them again).  `--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (float32 / float64, 56 MB at
+most in all; larger arrays as a fixed, seeded sample, see dump_outputs).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -178,7 +183,12 @@ def parse():
     ap.add_argument("--chunks", type=int, default=4, help="pieces of the overlapped all-gather of the reconstructed output")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: skip the second loop with the all-gather in the step")
     ap.add_argument("--dump", default="", help="validation: rank 0 saves the (gathered) reconstructed output as .npy")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64, a seeded sample of "
+                         "arrays too large for the budget), so that two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: the `also` block, the PCIe-inclusive rate and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg (and the PCIe-inclusive rate)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--gather", nargs="?", const="auto", default="auto", choices=["p2p", "collective", "auto"],
                     help="N > 1: exchange schedule of the all-gather loop -- grouped point-to-point (every piece lands in place), "
@@ -190,7 +200,7 @@ def parse():
                     help="N > 1: seconds the second loop (all-gather inside the step) may take before every rank abandons it; rank 0 "
                          "then prints the line of the main loop with the failure noted (`exchange_abandoned`) and all ranks exit 4")
     ap.add_argument("--no-also", action="store_true",
-                    help="skip the `also` block (the other headline workloads, hipEvent-timed in the same run; N = 1 only)")
+                    help="--full: skip the `also` block (the other headline workloads, hipEvent-timed in the same run; N = 1 only)")
     return ap.parse_args()
 
 
@@ -505,6 +515,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         W.step, W.step_gather = step, step_gather
         W.check = lambda: float((xh - x).abs().max() / x.abs().max())
         W.output = lambda gathered: full if gathered else xh
+        W.outputs = lambda: {"wpdall" if kind == "wpd" else "wptall": y, "iwpdall" if kind == "wpd" else "iwptall": xh}
         W.info = dict(fwd_bytes=fb, inv_bytes=es * npts * Bl * 2, fwd_flops=flops, samples=npts * Bl, bound="hbm",
                       gather_bytes=es * npts * (B_out - Bl))
         W.keep = (x, y, full)
@@ -524,6 +535,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         W.step = step
         W.check = lambda: float((xh - x).abs().max() / x.abs().max())
         W.output = lambda gathered: xh
+        W.outputs = lambda: {"sdwtall": xw, "isdwtall": xh}
         fb = es * n * Bl * (L + 2)
         W.info = dict(fwd_bytes=fb, inv_bytes=fb, fwd_flops=4.0 * F * n * L * Bl, samples=n * Bl, bound="hbm")
         W.keep = (x, xw, xh, q)
@@ -573,6 +585,8 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         W.step, W.step_gather = step, step_gather
         W.check = lambda: float((xh - x).abs().max() / x.abs().max())
         W.output = lambda gathered: full if gathered else xh
+        # the leaves are resident one chunk at a time: after a step they are the last chunk's
+        W.outputs = lambda: {"swptall_last_chunk": xw[..., :chunks[-1][1] - chunks[-1][0]], "iswptall": xh}
         fb = es * n * CH * (1 + (1 << L))
         W.info = dict(fwd_bytes=fb, inv_bytes=fb, fwd_flops=((1 << L) - 1) * 4.0 * F * n * CH, samples=n * Bl, bound="hbm",
                       launch_unit="one resident chunk of %d signals" % CH, gather_bytes=es * n * (B_out - Bl))
@@ -619,6 +633,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         W.extra = lambda: {"min_rel_cost_gap": state.get("gap"), "tree_split_nodes": int(state["tree"].sum())}
         W.check = lambda: 0.0 if wx.isvalidtree(torch.empty(n), state["tree"]) else 1.0
         W.output = lambda gathered: torch.from_numpy(state["tree"].astype("float64"))
+        W.outputs = lambda: {"jbb_moment_sum": state["s"], "jbb_moment_sumsq": state["q"], "bestbasistree": torch.from_numpy(state["tree"])}
         flops = acwpd_jbb_min_flops(n, L, F) * Bl
         W.info = dict(fwd_bytes=es * (n * Bl + 2 * n * ncols), inv_bytes=es * 2 * n * ncols, fwd_flops=flops, samples=n * Bl,
                       bound="fp64", flops_note="minimal algorithm: per depth the periodised autocorrelation filter (odd lags and the "
@@ -652,6 +667,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         def check():
             t = state["trees"][:4].cpu().numpy().astype(bool)
             return 0.0 if all(wx.isvalidtree(torch.empty(n), t[i]) for i in range(4)) else 1.0
+        outputs = lambda: {"wpdall": xw, "bestbasistreeall": state["trees"].t()}      # trees: (B, n - 1) row-major, i.e. (n - 1, B)
         ncost = (1 << (L + 1)) - 1
         W.info = dict(fwd_bytes=es * (n * (L + 1) + ncost) * B + (n - 1) * B, inv_bytes=es * n * (L + 2) * B,
                       fwd_flops=4.0 * n * (L + 1) * B, samples=n * B, bound="hbm")
@@ -667,6 +683,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
             state["y2"] = wx.denoiseall(wx.dwtall(x, wt, L), "dwt", wt, L=L, dnt=dnt)
 
         check = lambda: float((state["y"] - state["y2"]).abs().max() / x.abs().max())
+        outputs = lambda: {"denoiseall_sig": state["y"], "denoiseall_dwt": state["y2"]}
         W.info = dict(fwd_bytes=es * 2 * n * B, inv_bytes=es * 4.5 * n * B, fwd_flops=(2 * 8.0 * F + 100.0) * n * B, samples=n * B, bound="hbm")
         W.keep = (x,)
     elif kind == "wpd_ldb":
@@ -687,6 +704,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
             g = state["G"]
             s = float(g[:, 0, :].sum().item())                       # root column: energies sum to 1 per class
             return abs(s - 4.0) / 4.0
+        outputs = lambda: {"wpdall": xw, "energy_map": state["G"]}
         W.info = dict(fwd_bytes=es * (n * (L + 1)) * (B + 4), inv_bytes=es * n * (L + 2) * B,
                       fwd_flops=2.0 * n * (L + 1) * B, samples=n * B, bound="hbm")
         W.keep = (x, xw)
@@ -702,6 +720,7 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
             state["xh"] = wx.isiwpdall(state["b"])
 
         check = lambda: float((state["xh"] - x).abs().max() / x.abs().max())
+        outputs = lambda: {"siwpdall_table": state["b"].Table, "siwpdall_costs": state["b"].Costs, "isiwpdall": state["xh"]}
         NS = sum(1 << min(j, d) for j in range(L + 1))
         NN = sum((1 << min(j, d)) << j for j in range(L + 1))
         # parents read once, every column written once, one cost per node (the costs of nodes of <= 256 samples
@@ -721,8 +740,46 @@ def make_workload(w, wx, torch, dev, rank, world, a, dist):
         legs.run("fwd", fwd)
         legs.run("inv", inv)
 
-    W.step, W.check = step, check
+    W.step, W.check, W.outputs = step, check, outputs
     return W
+
+
+DUMP_BUDGET = 56_000_000        # bytes of array data in all (under 64 MB with the .npy headers)
+DUMP_SEED = 20251015
+
+
+def dump_sample(t, budget, seed=DUMP_SEED):
+    """`t` (Julia shape, a torch tensor) as a float32 / float64 numpy array of at most `budget` bytes: the whole array if it
+    fits; else a seeded choice of columns of the last (batch) axis, in order, if at least 8 of them fit; else a seeded
+    choice of elements in column-major order, sorted (1-D).  The choice depends on the shape, the budget and the seed only."""
+    import numpy as np
+    import torch
+    t = t.detach()
+    if t.dtype not in (torch.float32, torch.float64):
+        t = t.to(torch.float32)                          # trees, status bytes: exact in float32
+    es = t.element_size()
+    n_all = t.numel()
+    if n_all * es <= budget:
+        return t.cpu().numpy()
+    rng = np.random.default_rng(seed)
+    col = n_all // t.shape[-1]
+    if t.dim() > 1 and 8 * col * es <= budget:
+        idx = np.sort(rng.choice(t.shape[-1], size=budget // (col * es), replace=False))
+        return t.index_select(t.dim() - 1, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+    idx = np.unique(rng.integers(0, n_all, size=budget // es))
+    flat = t.permute(*reversed(range(t.dim()))) if t.dim() > 1 else t      # column-major storage as one row-major run
+    if not flat.is_contiguous():
+        flat = flat.contiguous()
+    return flat.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+
+
+def dump_outputs(outputs, out_dir):
+    """DIR/<name>.npy for every output of the last timed step, the budget split evenly between them"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), dump_sample(t, DUMP_BUDGET // len(outputs)))
+
 
 def acwpd_jbb_min_flops(n, L, F):
     """Float64 operations per signal of acwpd + the two JBB moments by the cheapest direct algorithm (an FMA = 2).
@@ -945,6 +1002,9 @@ def main():
 
     stage["at"] = "timed steps"
     elapsed, per_rank, legs = timed(W.step)
+    if a.dump_outputs and rank == 0:
+        stage["at"] = "dump of the outputs"
+        dump_outputs(W.outputs(), a.dump_outputs)
     fwd_ms, inv_ms = legs.ms("fwd"), legs.ms("inv")
     fwd_avg = sum(fwd_ms) / len(fwd_ms)
     inv_avg = sum(inv_ms) / len(inv_ms)
@@ -1132,7 +1192,7 @@ def main():
             np.save(a.dump, outp.detach().cpu().numpy())
 
     out = build_line(gather) if rank == 0 else None
-    if rank == 0:
+    if rank == 0 and a.full:
         if world == 1 and not a.no_also and not a.batch and a.workload == "cfg2":
             W.keep = None
             del W, legs, warm

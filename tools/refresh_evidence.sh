@@ -14,7 +14,7 @@ for w in $WL; do
 done
 python tools/collect_evidence.py $TAG ${2:-r02} > /dev/null 2>&1      # profiles/traffic.json of this build, read by bench.py
 for w in $WL; do
-  NA=--no-also; [ $w = cfg2 ] && NA=
+  NA="--full --no-also"; [ $w = cfg2 ] && NA=--full      # the side measurements: CPU baseline, PCIe rate, cfg2's also block
   timeout 600 python bench.py --workload $w $NA > gpurun_out/bench_$TAG/$w.json 2> gpurun_out/bench_$TAG/$w.err
   tail -c 200 gpurun_out/bench_$TAG/$w.json; echo
 done
