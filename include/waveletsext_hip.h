@@ -343,6 +343,23 @@ int wx_emd_measure_weighted_f64(const double *X, const double *W, int64_t nk, in
 int wx_emd_measure_weighted_f32(const float *X, const float *W, int64_t nk, int64_t N, const int32_t *cls, int nc,
                                 float *D, void *stream);
 
+/* Least statistically dependent basis (LSDB), differential-entropy costs.  X is a packet table with the signal axis last.
+ * wx_lsdb_entropy_*:  E[e] (Float64) = coefcost(X[e, :], DifferentialEntropyCost()) for every row e of X seen as (nk, N),
+ *     bestbasis/bestbasis_costs.jl:135-155 (average shifted histogram with M = 50 and Base's start:step:stop length, both
+ *     restated in csrc/wx_lsdb.hip, parity unpinned);
+ * wx_lsdb_costs_*:    tree_costs(X::Array{T,3}, LSDB(redundant)) bestbasis/bestbasis_tree.jl:104-126, X (n, k, N): 2^k - 1
+ *     costs (wpd table) or k (redundant, column i weighted 1/2^depth(i)); node sums in Float64, bestbasis_costs.jl:157-164;
+ * wx_lsdb_costs2d_*:  tree_costs(X::Array{T,4}, LSDB(redundant)) :128-147, X (m, n, k, N): (4^k - 1)/3 costs or k
+ *     (redundant, weight 1/4^depth(i)).
+ * Host or device pointers.  A row the reference throws for (max == min, N == 1, a non-finite value) returns WX_EARG and
+ * names the first such coefficient (and node); the call reads its status word back, so it returns with the stream idle. */
+int wx_lsdb_entropy_f64(const double *X, int64_t nk, int64_t N, double *E, void *stream);
+int wx_lsdb_entropy_f32(const float *X, int64_t nk, int64_t N, double *E, void *stream);
+int wx_lsdb_costs_f64(const double *X, int64_t n, int64_t k, int64_t N, int redundant, double *costs, void *stream);
+int wx_lsdb_costs_f32(const float *X, int64_t n, int64_t k, int64_t N, int redundant, float *costs, void *stream);
+int wx_lsdb_costs2d_f64(const double *X, int64_t m, int64_t n, int64_t k, int64_t N, int redundant, double *costs, void *stream);
+int wx_lsdb_costs2d_f32(const float *X, int64_t m, int64_t n, int64_t k, int64_t N, int redundant, float *costs, void *stream);
+
 /* 3-D discrete wavelet transform of a batch of cubes: dwtall / idwtall on 4-D arrays (dwt/dwt_all.jl:39-54, 95-110 over
  * Wavelets.jl's 3-D dwt! / idwt!, which is not vendored: the separable pyramid -- one analysis step along dimension 1,
  * 2, 3 of the low-pass sub-cube per level -- is restated from its published source).  x, y: (n1, n2, n3, batch)

@@ -1,5 +1,5 @@
 """The callers' side of the path at several lengths: denoiseall (dwt -> per-signal MAD -> threshold -> idwt, Denoising.jl:651-712; from the signals and from their coefficients),
-bestbasistreeall(wpdall(x), BB()) (BestBasis.jl:253-262) and getbasiscoefall along one tree (Utils.jl:199-225), Float64, db4, batches of about 1 GiB of
+bestbasistreeall(wpdall(x), BB()) (BestBasis.jl:253-262), bestbasistree with JBB and LSDB (:185-201) and getbasiscoefall along one tree (Utils.jl:199-225), Float64, db4, batches of about 1 GiB of
 signal (and packet tables of 1 GiB).  Times in ms and effective GB/s on signal-read-once + written-once bytes (denoise) or on the table's bytes."""
 import os
 import sys
@@ -38,6 +38,8 @@ def scan(lengths=None):
         print("f64 n %6d getbasiscoefall(pyramid)   %7.3f ms (%4.1f %% on 2 x signal bytes)" % (n, t, 100 * 2.0 * n * Bq * 8 / (t * 1e-3) / HBM_PEAK), flush=True)
         t = timed(torch, lambda: wx.bestbasistree(tab, wx.JBB()))
         print("f64 n %6d bestbasistree(JBB)         %7.3f ms (%4.1f %% on the table's bytes)" % (n, t, 100 * tb / (t * 1e-3) / HBM_PEAK), flush=True)
+        t = timed(torch, lambda: wx.bestbasistree(tab, wx.LSDB()))
+        print("f64 n %6d bestbasistree(LSDB)        %7.3f ms (%4.1f %% on the table's bytes)" % (n, t, 100 * tb / (t * 1e-3) / HBM_PEAK), flush=True)
         labels = [i % 3 for i in range(Bq)]
         f = wx.LocalDiscriminantBasis(wt=wt, n_features=10)
         t = timed(torch, lambda: wx.fit_transform(f, xq, labels), calls=2, batches=2)

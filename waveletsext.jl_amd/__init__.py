@@ -23,7 +23,8 @@ from .acwt import (acdwt, acdwt_, acdwtall, iacdwt, iacdwt_, iacdwtall, acwpt, a
                    autocorr, pfilter, qfilter, make_acqmfpair, make_acreverseqmfpair)
 from .bestbasis import (JBB, LoglpCost, NormCost, tree_costs, bestbasistree, bestbasis_treeselection,   # noqa: F401
                         jbb_moments, costs_from_moments, acwpd_jbb_moments,
-                        BB, ShannonEntropyCost, LogEnergyEntropyCost, bestbasistreeall)
+                        BB, ShannonEntropyCost, LogEnergyEntropyCost, bestbasistreeall,
+                        LSDB, DifferentialEntropyCost, lsdb_entropy)
 from .denoising import (HardTH, SoftTH, SemiSoftTH, SteinTH, VisuShrink, SureShrink, RelErrorShrink,   # noqa: F401,E402
                         noisest, threshold, denoise, denoiseall, surethreshold, relerrorthreshold,
                         surethresholdall, relerrorthresholdall)

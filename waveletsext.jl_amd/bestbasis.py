@@ -1,7 +1,7 @@
-"""Joint best basis (JBB): host-side mirror of the JBB slice of the reference's `BestBasis`
-module (src/mod/BestBasis.jl:59-83,128-140,194-201; bestbasis/bestbasis_tree.jl:43-46,150-180;
-bestbasis/bestbasis_costs.jl:44-57,127-132) for 1-D signals.  Moments and costs run on the GPU;
-the bottom-up tree selection is the library's tiny host routine."""
+"""Best basis: host-side mirror of the reference's `BestBasis` module for the three best-basis types, JBB
+(src/mod/BestBasis.jl:59-83,128-140,194-201; bestbasis/bestbasis_tree.jl:43-46,150-180; bestbasis/bestbasis_costs.jl:44-57,
+127-132), BB (bestbasis_tree.jl:60-63, 210-258) and LSDB (bestbasis_tree.jl:24-27, 104-147; bestbasis_costs.jl:66, 135-164).
+Moments, entropies and costs run on the GPU; the bottom-up tree selection is the library's tiny host routine."""
 import ctypes
 
 import numpy as np
@@ -33,6 +33,20 @@ class ShannonEntropyCost:
 
 class LogEnergyEntropyCost:
     """bestbasis_costs.jl:86"""
+
+
+class DifferentialEntropyCost:
+    """bestbasis_costs.jl:66, the LSDB cost (coefcost :135-164)"""
+
+
+class LSDB:
+    """Least statistically dependent basis, bestbasis_tree.jl:24-27"""
+
+    def __init__(self, cost=None, redundant=False):
+        self.cost = DifferentialEntropyCost() if cost is None else cost
+        if not isinstance(self.cost, DifferentialEntropyCost):
+            raise TypeError("LSDB cost must be DifferentialEntropyCost")
+        self.redundant = bool(redundant)
 
 
 class BB:
@@ -90,6 +104,32 @@ def costs_from_moments(s, q, Ntot, method=None):
     costs = s.new((ncost,))
     _call("wx_jbb_costs", s.suffix, s.ptr, q.ptr, int(Ntot), n, k, int(method.redundant), kind, p, costs.ptr,
           s.stream())
+    return costs.arr
+
+
+def lsdb_entropy(X):
+    """coefcost(X[e, :], DifferentialEntropyCost()) (bestbasis_costs.jl:135-155) of every row e of X seen as (nk, N), the
+    signal axis last: Float64 array of shape X.shape[:-1], same kind as X."""
+    Xa = Arg(X)
+    shp, N = Xa.shape[:-1], Xa.shape[-1]
+    E = Xa.new(shp, dtype=np.float64)
+    _call("wx_lsdb_entropy", Xa.suffix, Xa.ptr, int(np.prod(shp, dtype=np.int64)), N, E.ptr, Xa.stream())
+    return E.arr
+
+
+def _lsdb_costs(Xa, method):
+    """tree_costs(X, LSDB(...)) bestbasis_tree.jl:104-147: X (n, k, N) or (n, m, k, N) -> costs, same kind and type as X"""
+    red = int(method.redundant)
+    if Xa.arr.ndim == 4:
+        n, m, k, N = Xa.shape
+        ncost = k if red else gettreelength(1 << k, 1 << k)
+        costs = Xa.new((ncost,))
+        _call("wx_lsdb_costs2d", Xa.suffix, Xa.ptr, n, m, k, N, red, costs.ptr, Xa.stream())
+    else:
+        n, k, N = Xa.shape
+        ncost = k if red else gettreelength(1 << k)
+        costs = Xa.new((ncost,))
+        _call("wx_lsdb_costs", Xa.suffix, Xa.ptr, n, k, N, red, costs.ptr, Xa.stream())
     return costs.arr
 
 
@@ -153,12 +193,17 @@ def bestbasistreeall(X, method=None):
 
 
 def tree_costs(X, method=None):
-    """tree_costs(X::Array{T,3}, method::JBB) bestbasis_tree.jl:150-180; tree_costs(X, ::BB) :210-258 (one signal)"""
+    """tree_costs(X::Array{T,3}, method::JBB) bestbasis_tree.jl:150-180; tree_costs(X, ::BB) :210-258 (one signal);
+    tree_costs(X, ::LSDB) :104-147"""
     method = JBB() if method is None else method
     if isinstance(method, BB):
         Xa = Arg(X)
         assert 2 <= Xa.arr.ndim <= 3
         return _bb_costs(Xa, method, False).arr
+    if isinstance(method, LSDB):
+        Xa = Arg(X)
+        assert 3 <= Xa.arr.ndim <= 4
+        return _lsdb_costs(Xa, method)
     if not isinstance(method, JBB):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED, "only the JBB best-basis type is on the device path")
     Xa = Arg(X)
@@ -204,8 +249,8 @@ def bestbasis_treeselection(costs, n, *args, return_gap=False):
 
 
 def bestbasistree(X, method=None):
-    """bestbasistree(X, JBB(...)) BestBasis.jl:194-201 (X is (n, k, N)); bestbasistree(X, BB(...)) :203-210 (one
-    signal, X is (n, k) or (n, m, k))"""
+    """bestbasistree(X, JBB(...)) BestBasis.jl:194-201 and bestbasistree(X, LSDB(...)) :185-192 (X is (n, k, N) or
+    (n, m, k, N)); bestbasistree(X, BB(...)) :203-210 (one signal, X is (n, k) or (n, m, k))"""
     method = JBB() if method is None else method
     Xa = Arg(X)
     if isinstance(method, BB):

@@ -11,6 +11,7 @@
 // all-reduce(sum) of [sum | sumsq].
 #include "wx_common.h"
 #include "wx_kernels.h"
+#include "wx_nodegeom.h"
 
 // sum[e] (+)= sum_b X[e, b];  sumsq[e] (+)= sum_b X[e, b]^2      (e in [0, nk), b in chunk)
 // x*x rounded on its own, as the reference's X.^2 (bestbasis_tree.jl:154): folding the square into the
@@ -91,15 +92,8 @@ __global__ __launch_bounds__(256) void k_jbb_costs(const T *__restrict__ sum, co
 {
     __shared__ double red[256];
     const int idx = blockIdx.x;                   // 0-based cost index
-    int col, off, len, depth;
-    if (redundant) {
-        col = idx; off = 0; len = n;
-        depth = 0; for (int t = idx + 1; t > 1; t >>= 1) ++depth;
-    } else {
-        depth = 0; for (int t = idx + 1; t > 1; t >>= 1) ++depth;   // heap order == (lvl, node) order
-        const int node = idx + 1 - (1 << depth);
-        col = depth; len = n >> depth; off = node * len;
-    }
+    const WxNode1d g = wx_node1d(idx, n, redundant);
+    const int col = g.col, off = g.off, len = g.len, depth = g.depth;
     double acc = 0.0;
     for (int i = threadIdx.x; i < len; i += blockDim.x) {
         const int64_t e = (int64_t)col * n + off + i;
@@ -132,17 +126,9 @@ __global__ __launch_bounds__(256) void k_jbb_costs2d(const T *__restrict__ sum, 
 {
     __shared__ double red[256];
     const int64_t idx = blockIdx.x;               // 0-based heap index
-    int depth = 0;
-    { int64_t t = 3 * (idx + 1) - 2; while (t >= 4) { t >>= 2; ++depth; } }
-    int64_t start = 1;
-    for (int t = 0; t < depth; ++t) start = 4 * start - 2;
-    const int64_t mort = idx + 1 - start;
-    int jr = 0, jc = 0;
-    for (int t = 0; t < depth; ++t) { jr |= (int)((mort >> (2 * t + 1)) & 1) << t; jc |= (int)((mort >> (2 * t)) & 1) << t; }
-    int r0, c0, nr, ncl;
-    int64_t slice;
-    if (redundant) { slice = idx; r0 = 0; c0 = 0; nr = m; ncl = n; }
-    else { slice = depth; nr = m >> depth; ncl = n >> depth; r0 = jr * nr; c0 = jc * ncl; }
+    const WxNode2d g = wx_node2d(idx, m, n, redundant);
+    const int64_t slice = g.slice;
+    const int r0 = g.r0, c0 = g.c0, nr = g.nr, ncl = g.ncl, depth = g.depth;
     double acc = 0.0;
     const int cnt = nr * ncl;
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) {

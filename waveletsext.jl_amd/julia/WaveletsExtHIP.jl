@@ -32,8 +32,8 @@ import WaveletsExt.SWT: sdwt, sdwt!, isdwt, isdwt!, swpt, swpt!, iswpt, iswpt!, 
                         sdwtall, isdwtall, swptall, iswptall, swpdall, iswpdall
 import WaveletsExt.ACWT: acdwt, acdwt!, iacdwt, iacdwt!, acwpt, acwpt!, iacwpt, iacwpt!, acwpd, acwpd!, iacwpd, iacwpd!,
                          acdwtall, iacdwtall, acwptall, iacwptall, acwpdall, iacwpdall
-import WaveletsExt.BestBasis: tree_costs, JBB, BB, LoglpCost, NormCost, ShannonEntropyCost, LogEnergyEntropyCost,
-                              bestbasis_treeselection, bestbasistreeall
+import WaveletsExt.BestBasis: tree_costs, JBB, BB, LSDB, LoglpCost, NormCost, ShannonEntropyCost, LogEnergyEntropyCost,
+                              DifferentialEntropyCost, bestbasis_treeselection, bestbasistreeall
 import WaveletsExt.Utils: getbasiscoef, getbasiscoefall
 import WaveletsExt.Denoising: surethreshold, relerrorthreshold
 import WaveletsExt.LDB: energy_map, discriminant_power, TimeFrequency, ProbabilityDensity, Signatures,
@@ -143,6 +143,8 @@ c_jbb_costs(T, s, q2, Ntot, sig::NTuple{1,Int}, k, red, kind, p, costs) = check(
 c_jbb_costs(T, s, q2, Ntot, sig::NTuple{2,Int}, k, red, kind, p, costs) = check(wx_jbb_costs2d(T, s, q2, Ntot, sig[1], sig[2], k, red, kind, p, costs, stream()))
 c_bb_costs(T, X, costs, sig::NTuple{1,Int}, k, N, red, kind) = check(wx_bb_costs(T, X, costs, sig[1], k, N, red, kind, stream()))
 c_bb_costs(T, X, costs, sig::NTuple{2,Int}, k, N, red, kind) = check(wx_bb_costs2d(T, X, costs, sig[1], sig[2], k, N, red, kind, stream()))
+c_lsdb_costs(T, X, sig::NTuple{1,Int}, k, N, red, costs) = check(wx_lsdb_costs(T, X, sig[1], k, N, red, costs, stream()))
+c_lsdb_costs(T, X, sig::NTuple{2,Int}, k, N, red, costs) = check(wx_lsdb_costs2d(T, X, sig[1], sig[2], k, N, red, costs, stream()))
 c_treeselect(T, costs, k, sig::NTuple{1,Int}, tmax, tree) = check(wx_treeselect(T, costs, k, sig[1], tmax, tree))
 c_treeselect(T, costs, k, sig::NTuple{2,Int}, tmax, tree) = check(wx_treeselect2d(T, costs, k, sig[1], sig[2], tmax, tree))
 
@@ -555,6 +557,14 @@ for N in 1:2
             s, q2 = jbb_moments(X)
             return costs_from_moments(s, q2, size(X)[end], method)
         end
+        # tree_costs(X, LSDB) for 1-D (n, k, N) and 2-D (n, m, k, N) decompositions (bestbasis_tree.jl:104-147): differential
+        # entropy of every coefficient row and the node sums on the device (a degenerate row throws ArgumentError)
+        function tree_costs(X::HIP{T,$(N + 2)}, method::LSDB) where T<:FT
+            sig = size(X)[1:end-2]; k = size(X)[end-1]
+            costs = Vector{T}(undef, jbb_ncost(sig, k, method.redundant))
+            c_lsdb_costs(T, raw(X), sig, k, size(X)[end], method.redundant, costs)
+            return costs
+        end
         # tree_costs(X, BB) of one decomposed signal (n, k) / (n, m, k) (bestbasis_tree.jl:210-258)
         function tree_costs(X::HIP{T,$(N + 1)}, method::BB) where T<:FT
             sig = size(X)[1:end-1]; k = size(X)[end]
@@ -586,6 +596,14 @@ bestbasis_treeselection(costs::HIP{T,1}, n::Integer, m::Integer, type::Symbol = 
 # bestbasistree(X, JBB) (BestBasis.jl:194-201), bestbasistree(X, BB) of one signal (:203-210)
 bestbasistree(X::HIP{T}, method::JBB = JBB()) where T<:FT = treeselect!(tree_costs(X, method), size(X)[1:end-2])
 bestbasistree(X::HIP{T}, method::BB) where T<:FT = treeselect!(tree_costs(X, method), size(X)[1:end-1])
+# bestbasistree(X, LSDB) (BestBasis.jl:185-192)
+bestbasistree(X::HIP{T}, method::LSDB) where T<:FT = treeselect!(tree_costs(X, method), size(X)[1:end-2])
+"coefcost(X[e, :], DifferentialEntropyCost()) (bestbasis_costs.jl:135-155) of every row e of X, signal axis last: Float64"
+function lsdb_entropy(X::HIP{T}) where T<:FT
+    E = Vector{Float64}(undef, prod(size(X)[1:end-1]))
+    check(wx_lsdb_entropy(T, raw(X), length(E), size(X)[end], E, stream()))
+    return reshape(E, size(X)[1:end-1])
+end
 # bestbasistreeall(X, BB) (BestBasis.jl:253-262): the costs of every signal and all N trees in one launch each
 function bestbasistreeall(X::HIP{T}, method::BB) where T<:FT
     @assert 3 ≤ ndims(X) ≤ 4
