@@ -293,12 +293,17 @@ int wx_treeselect_batch_f32(float *costs, int64_t ncost, int64_t m, int64_t n, i
  * k = 1 for dwt / wpt leaves, L+1 for sdwt / acdwt, 2^(L+1)-1 for swpd / acwpd.
  * wx_noisest_*: noisest(x, redundant, tree) Denoising.jl:214-232 = Wavelets.Threshold.mad!(dr)/0.6745 for every
  * signal, dr = rows [row_lo, n) of column `col` (the caller resolves finestdetailrange, Utils.jl:416-436);
- * exact order statistics (radix select in LDS; over a global-memory copy for more than 128 KiB of details), sigma has `batch` entries.
+ * exact order statistics (sorting networks, counting in registers, value-bucket selection in LDS or over a global-memory copy for
+ * more than 128 KiB of details), sigma has `batch` entries.  Non-finite details as Statistics.median!: sigma is NaN when a detail is
+ * NaN or the median is +-Inf or NaN (half the details one infinity, or middle(-Inf, Inf): the deviations then hold Inf - Inf);
+ * otherwise +-Inf details, and finite ones whose deviations overflow the type, rank as +Inf deviations (sigma may be +Inf).
  * wx_threshold_*: Y = Wavelets.Threshold.threshold(X, TH, t) on rows [row_lo, n) of the columns with
  * colmask != 0 (NULL = all), everything else copied; Y == X thresholds in place (threshold!) and touches only the
  * selected elements: th_kind 0 HardTH, 1 SoftTH, 2 SemiSoftTH, 3 SteinTH; t holds nt = 1 or `batch`
- * thresholds (sigma_i * dnt.t).  Wavelets.jl is not vendored: mad! and the threshold loops are restated from
- * its source.  Pointers may be host or device.
+ * thresholds (sigma_i * dnt.t).  A NaN or +Inf threshold, and 2|x| or 2t above the largest finite value, follow the
+ * loops as written: HardTH drops +-Inf at t = +Inf and keeps everything at t = NaN; SoftTH gives NaN for |x| = t = +Inf.
+ * Wavelets.jl is not vendored: mad! and the threshold loops are restated from its source (the non-finite cases are
+ * unpinned).  Pointers may be host or device.
  * ------------------------------------------------------------------------------------------ */
 int wx_noisest_f64(const double *X, int64_t n, int64_t k, int64_t batch, int64_t row_lo, int64_t col, double *sigma,
                    void *stream);
@@ -377,8 +382,9 @@ int wx_idwt3d_f32(const float *x, float *y, int64_t n1, int64_t n2, int64_t n3, 
  * VisuShrink family: xhat[:, i] = idwt(threshold(dwt(x[:, i], wt, L), th_kind, sigma_i * t), wt, L) with sigma_i = noisest(dwt(x[:, i])) =
  * mad(finest detail coefficients) / 0.6745 (Denoising.jl:214-232), t = dnt.t (VisuShrink: sqrt(2 log n)), th_kind as wx_threshold_*.
  * undersmooth != 0 (smooth = :undersmooth) leaves the coarsest scaling coefficients alone.  sigma (optional, host or device, batch values)
- * receives the noise estimates.  Float64 signals of 1024 ... 4096 samples with filters of up to 8 taps and the Hard / Soft / SemiSoft rules
- * take ONE pass (signal in, denoised signal out: the coefficients never leave the registers); every other case runs the three steps
+ * receives the noise estimates, with the non-finite semantics of wx_noisest_* and wx_threshold_*.  Float64 signals of 64 ... 4096 samples,
+ * L >= 1, a filter of up to 20 taps with a lattice factorisation and the Hard / Soft / SemiSoft rules (batches of at least one
+ * wavefront's signals) take ONE pass (signal in, denoised signal out: the coefficients never leave the registers); every other case runs the three steps
  * wx_wpt1d_* -> wx_noisest_* -> wx_iwpt1d_thresh_* on stream-ordered scratch, so the result does not depend on which applies. */
 int wx_denoiseall_sig_f64(const double *x, double *xhat, int64_t n, int L, int64_t batch, const double *qmf, int F, int th_kind,
                           double t, int undersmooth, double *sigma, void *stream);

@@ -1299,6 +1299,9 @@ static int FN(wxo_cmp)(const void *a, const void *b)
 }
 static T FN(wxo_median_inplace)(T *y, int64_t n)
 {
+    /* Statistics.median!: NaN as soon as any value is NaN (the comparator below is no ordering then) */
+    for (int64_t i = 0; i < n; i++)
+        if (y[i] != y[i]) return (T)NAN;
     qsort(y, (size_t)n, sizeof(T), FN(wxo_cmp));
     if (n & 1) return y[n / 2];
     return (T)((T)(y[n / 2 - 1] / 2) + (T)(y[n / 2] / 2));

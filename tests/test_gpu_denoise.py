@@ -4,6 +4,7 @@ hard threshold are exact (==); reconstructed signals within 1e-10 / 1e-5."""
 import numpy as np
 import pytest
 
+import noisest_ref
 from helpers import TOL, relerr
 
 pytestmark = pytest.mark.gpu
@@ -276,6 +277,15 @@ def test_noisest_counting_kernels_every_size(wx, oracle, dtype):
         v[n - 5, 1] = np.nan
         sig = wx.to_numpy(dn._noisest(dn.Arg(v), True, "dwt", None))
         assert np.isnan(sig[1]) and sig[0] == oracle.noisest(v[:, 0], False) and sig[2] == oracle.noisest(v[:, 2], False)
+        # +-Inf and overflowing deviations (tests/noisest_ref.py): every case beside a clean signal, bit for bit with the oracle, NaN matching NaN
+        cs = noisest_ref.cases(n // 2, dtype, rng)
+        v = np.asfortranarray(rng.standard_normal((n, 2 * len(cs) + 1)).astype(dtype))
+        for j, c in enumerate(cs.values()):
+            v[n // 2:, 2 * j + 1] = c
+        sig = wx.to_numpy(dn._noisest(dn.Arg(v), True, "dwt", None))
+        for i in range(v.shape[1]):
+            exp = np.array([oracle.noisest(v[:, i], False)], dtype=dtype)
+            assert noisest_ref.same(sig[i:i + 1], exp) and noisest_ref.same(exp, np.array([noisest_ref.noisest_range(v[n // 2:, i])])), (n, i, dtype)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

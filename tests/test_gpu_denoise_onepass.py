@@ -112,6 +112,15 @@ def test_onepass_constant_nan_and_small_batches(wx, oracle):
         assert np.isnan(sig2[4])
         for i in (3, 5, x.shape[1] - 1):
             assert sig2[i] == sig[i] and (y2[:, i] == y[:, i]).all()
+        # +-Inf samples: the lattice's rotations make NaN where the direct convolution gives +-Inf (a difference by construction), so only
+        # the neighbours are pinned -- untouched, and the run ends
+        xi = x.copy(order="F")
+        xi[n // 3, 4] = np.inf
+        xi[n // 2, 6] = -np.inf
+        xi[:, 7] = np.inf
+        y3, sig3 = _sigma_c(wx, xi, wt, L)
+        for i in (3, 5, 8, x.shape[1] - 1):
+            assert sig3[i] == sig[i] and (y3[:, i] == y[:, i]).all()
         # batches below the signals per wavefront (the separate kernels take them) and a single signal through denoise()
         for B in (1, 2, 3):
             yb, sb = _sigma_c(wx, np.asfortranarray(x[:, :B]), wt, L)

@@ -65,7 +65,10 @@ template <typename T> __device__ __forceinline__ T wx_thresh(T v, T tt, int th_k
         // semisoft (Gao-Bruce, upper knee at 2t): 0 below t, sign(x) * 2(|x| - t) up to 2t, x above
         const T av = (T)fabs((double)v);
         if (av > (T)((T)2 * tt)) return v;
-        const T tmp = (T)((T)((T)2 * av) - (T)((T)2 * tt));
+        // 2|x| rounds on its own, to +Inf above the largest finite value / 2 like the rule's: opaque, or -ffp-contract=fast fuses it
+        T av2 = (T)2 * av;
+        asm volatile("" : "+v"(av2));
+        const T tmp = (T)(av2 - (T)((T)2 * tt));
         return tmp < (T)0 ? (T)0 : (T)(sg * tmp);
     }
     const T sh = (T)((T)1 - (T)((T)(tt * tt) / (T)(v * v)));

@@ -56,7 +56,7 @@ __global__ __launch_bounds__(256) void k_threshold(T *__restrict__ X, int n, int
         T *p = X + (sig * k + (cols ? cols[c] : c)) * (int64_t)n + r;
         const T v = *p, tt = per_signal ? t[sig] : t[0];
         const T out = wx_thresh<T>(v, tt, th_kind);
-        if (out != v || th_kind != 0) *p = out;
+        if (out != v || th_kind != 0 || v == (T)0) *p = out;        // (-0 == +0: the rule's zero is +0)
     }
 }
 
@@ -65,7 +65,8 @@ __global__ __launch_bounds__(256) void k_threshold(T *__restrict__ X, int n, int
 // is monotone, so the k-th smallest lies in the bucket where the running count crosses k.  One histogram pass
 // (1024 buckets: coefficients spread over them, so the LDS atomics do not pile up on one word) leaves a handful
 // of candidates, which are ranked directly.  Degenerate data (everything in one bucket) narrows [lo, hi] to that
-// bucket's own min / max and repeats; equal candidates end the search.  No arithmetic on the result: exact.
+// bucket's own min / max and repeats; equal candidates end the search.  No arithmetic on the result: exact.  Infinite bounds are split off
+// before the bucketing, and the offsets are scaled so that lo and hi always land in different buckets: every input ends (wx_select_kth).
 constexpr int WX_NB = 1024;       // buckets
 constexpr int WX_LST = 256;       // candidates ranked directly
 
@@ -102,17 +103,63 @@ __device__ void wx_block_minmax(const T *v, int cnt, P pred, WxSelScratch *S, T 
     mn = (T)m0; mx = (T)m1;
 }
 
-// k-th smallest (0-based) of v[0..cnt); all threads return the same value
+// block-wide #{i in [0, cnt): pred(v[i])}; every thread gets the result
+template <typename T, typename P>
+__device__ __forceinline__ int wx_block_count(const T *v, int cnt, P pred, WxSelScratch *S)
+{
+    int c = 0;
+    for (int i = threadIdx.x; i < cnt; i += blockDim.x) c += pred(v[i]) ? 1 : 0;
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    const int w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) S->ired[4 + w] = c;
+    __syncthreads();
+    int s = 0;
+    for (int j = 0; j < (int)(blockDim.x >> 6); ++j) s += S->ired[4 + j];
+    __syncthreads();
+    return s;
+}
+
+// k-th smallest (0-based) of v[0..cnt); all threads return the same value.  Every pass ends the search or removes at least one distinct value
+// from the candidates [lo, hi]: an infinite end is split off by counting its copies (they hold rank kk, or they leave), and the bucketing then
+// works on finite lo < hi, puts lo in bucket 0 and hi in bucket WX_NB - 1, so the bucket it narrows to misses lo or hi.
 template <typename T>
 __device__ T wx_select_kth(const T *v, int cnt, int k, WxSelScratch *S)
 {
+    const T inf = (T)INFINITY;
     T lo, hi;
     wx_block_minmax(v, cnt, [](T) { return true; }, S, lo, hi);
     int kk = k;                                       // rank among the candidates lo <= x <= hi
     for (;;) {
         if (!(lo < hi)) return lo;                    // all candidates equal (or NaN-degenerate)
-        const double scale = (double)WX_NB / ((double)hi - (double)lo);
-        auto bucket = [&](T x) { int b = (int)(((double)x - (double)lo) * scale); return b < WX_NB ? b : WX_NB - 1; };
+        if (lo == -inf) {
+            // rare: the copies of -Inf hold ranks 0 ... c - 1; else the search goes on above them
+            const int c = wx_block_count(v, cnt, [](T x) { return x == -(T)INFINITY; }, S);
+            if (kk < c) return lo;
+            kk -= c;
+            const T chi = hi;
+            T nlo, nhi;
+            wx_block_minmax(v, cnt, [chi](T x) { return x > -(T)INFINITY && x <= chi; }, S, nlo, nhi);
+            lo = nlo;
+            continue;
+        }
+        if (hi == inf) {
+            // rare: the c finite candidates rank below the copies of +Inf
+            const T clo = lo;
+            if (kk >= wx_block_count(v, cnt, [clo](T x) { return x >= clo && x < (T)INFINITY; }, S)) return hi;
+            T nlo, nhi;
+            wx_block_minmax(v, cnt, [clo](T x) { return x >= clo && x < (T)INFINITY; }, S, nlo, nhi);
+            hi = nhi;
+            continue;
+        }
+        // finite lo < hi.  The offsets are taken on the values times sh: 1, or 1/2 where hi - lo overflows, or 2^900 where WX_NB / (hi - lo)
+        // would (then every candidate is below 2^-947 in magnitude and the scaling is exact).  The scale is finite, x -> (x sh - lo sh) scale
+        // rounds monotonically, lo maps to 0 and hi to WX_NB up to rounding: buckets 0 and WX_NB - 1.  (sh = 1 is the plain x - lo.)
+        const double dr = (double)hi - (double)lo;
+        const double sh = !(dr <= 1.7976931348623157e308) ? 0.5 : (dr < 0x1p-1000 ? 0x1p900 : 1.0);
+        const double losh = (double)lo * sh;
+        const double scale = (double)WX_NB / ((double)hi * sh - losh);
+        auto bucket = [&](T x) { int b = (int)(((double)x * sh - losh) * scale); return b < WX_NB ? b : WX_NB - 1; };
         for (int i = threadIdx.x; i < WX_NB; i += blockDim.x) S->hist[i] = 0;
         __syncthreads();
         for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
@@ -189,7 +236,7 @@ template <typename T> __device__ T wx_median_lds(const T *v, int cnt, WxSelScrat
     for (int j = 1; j < (int)(blockDim.x >> 6); ++j) { m = S->red[j] < m ? S->red[j] : m; tot += S->ired[4 + j]; }
     __syncthreads();
     const T b = tot >= cnt / 2 + 1 ? a : (T)m;
-    return (T)((T)(a / (T)2) + (T)(b / (T)2));
+    return dn_middle<T>(a, b);
 }
 
 // one workgroup per signal: median, absolute deviations, median again -- exact order statistics, so the result
@@ -209,10 +256,15 @@ __global__ __launch_bounds__(256) void k_mad(const T *__restrict__ X, int64_t si
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) nan |= v[i] != v[i];
     nan = __syncthreads_or(nan);
     const T m = wx_median_lds<T>(v, cnt, &S);
+    // a median of +-Inf or NaN: the deviations hold Inf - Inf = NaN, and so does Statistics.median! of them (the same for the whole block)
+    if (nan || !(fabs((double)m) < (double)INFINITY)) {
+        if (threadIdx.x == 0) sigma[blockIdx.x] = (T)__builtin_nan("");
+        return;
+    }
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) v[i] = (T)fabs((double)(T)(v[i] - m));
     __syncthreads();
     const T r = wx_median_lds<T>(v, cnt, &S);
-    if (threadIdx.x == 0) sigma[blockIdx.x] = nan ? (T)__builtin_nan("") : (T)(r / (T)0.6745);
+    if (threadIdx.x == 0) sigma[blockIdx.x] = (T)(r / (T)0.6745);
 }
 
 // short detail ranges (at most 512 coefficients: signals up to 1024 samples at the finest level): ONE WAVEFRONT per signal, four per
@@ -237,7 +289,7 @@ __global__ __launch_bounds__(256) void k_mad_wave(const T *__restrict__ X, int64
     for (int u = 0; u < E; ++u) nan = nan || e[u] != e[u];
     const bool any_nan = __builtin_amdgcn_ballot_w64(nan) != 0;          // every comparison with a NaN is false: its rank would be 0, the others' ranks ignore it
     const int k0 = (cnt - 1) / 2;
-    T med = (T)0;
+    T med = (T)0, med0 = (T)0;
     for (int round = 0; round < 2; ++round) {
 #pragma unroll
         for (int u = 0; u < E; ++u) { const int i = lane + 64 * u; if (i < cnt) v[i] = e[u]; }
@@ -264,14 +316,16 @@ __global__ __launch_bounds__(256) void k_mad_wave(const T *__restrict__ X, int64
         __builtin_amdgcn_wave_barrier();
         const T a = v[512];
         const T b = (cnt & 1) ? a : v[513];
-        med = (cnt & 1) ? a : (T)((T)(a / (T)2) + (T)(b / (T)2));   // Statistics.median!: middle(a, b) = a/2 + b/2
+        med = (cnt & 1) ? a : dn_middle<T>(a, b);                   // Statistics.median!: middle(a, b) = a/2 + b/2
         __builtin_amdgcn_wave_barrier();
         if (round == 0) {
+            med0 = med;
 #pragma unroll
             for (int u = 0; u < E; ++u) e[u] = (T)fabs((double)(T)(e[u] - med));
         }
     }
-    if (lane == 0) sigma[sig] = any_nan ? (T)__builtin_nan("") : (T)(med / (T)0.6745);
+    // the first median +-Inf or NaN: NaN deviations (Inf - Inf), whose median is NaN; the counting would rank around them
+    if (lane == 0) sigma[sig] = any_nan || !(fabs((double)med0) < (double)INFINITY) ? (T)__builtin_nan("") : (T)(med / (T)0.6745);
 }
 
 // 65 ... 512 coefficients (signals of 256 ... 1024 samples at the finest level; built up to 2048), round 6: ONE WAVEFRONT SORTS the values in its registers.
@@ -373,14 +427,15 @@ __global__ __launch_bounds__(256) void k_mad_sort(const T *__restrict__ X, int64
     const int k0 = (cnt - 1) / 2;
     const int base = sub * PL * E;                                    // slot 0 of this lane's signal
     const T a = mad_pick<T, E>(r, base + k0), b = mad_pick<T, E>(r, base + k0 + ((cnt & 1) ? 0 : 1));
-    const T med = (cnt & 1) ? a : (T)((T)(a / (T)2) + (T)(b / (T)2));
+    const T med = (cnt & 1) ? a : dn_middle<T>(a, b);
     // |v - med| of the sorted values: falls, then rises (the slots beyond cnt stay +Inf at the end): one bitonic merge sorts it
 #pragma unroll
     for (int u = 0; u < E; ++u) r[u] = (T)fabs((double)(T)(r[u] - med));
     mad_merge<T, E, P, false>(r, wl);
     const T a2 = mad_pick<T, E>(r, base + k0), b2 = mad_pick<T, E>(r, base + k0 + ((cnt & 1) ? 0 : 1));
-    const T mad = (cnt & 1) ? a2 : (T)((T)(a2 / (T)2) + (T)(b2 / (T)2));
-    if (lane == 0 && live) sigma[sig] = any_nan ? (T)__builtin_nan("") : (T)(mad / (T)0.6745);
+    const T mad = (cnt & 1) ? a2 : dn_middle<T>(a2, b2);
+    // a median of +-Inf or NaN: NaN deviations (Inf - Inf), whose median is NaN -- the network's min / max would drop them
+    if (lane == 0 && live) sigma[sig] = any_nan || !(fabs((double)med) < (double)INFINITY) ? (T)__builtin_nan("") : (T)(mad / (T)0.6745);
 }
 
 // 256 ... 4096 coefficients (signals of 512 ... 8192 samples at the finest level), round 6: ONE WAVEFRONT per signal keeps the values in NR = cnt / 64
@@ -454,11 +509,15 @@ __global__ __launch_bounds__(256) void k_mad_g(const T *__restrict__ X, int64_t 
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) nan |= x[i] != x[i];
     nan = __syncthreads_or(nan);
     const T m = wx_median_lds<T>(x, cnt, &S);
+    if (nan || !(fabs((double)m) < (double)INFINITY)) {                 // NaN among the deviations: as k_mad
+        if (threadIdx.x == 0) sigma[blockIdx.x] = (T)__builtin_nan("");
+        return;
+    }
     for (int i = threadIdx.x; i < cnt; i += blockDim.x) v[i] = (T)fabs((double)(T)(x[i] - m));
     __threadfence_block();
     __syncthreads();
     const T r = wx_median_lds<T>(v, cnt, &S);
-    if (threadIdx.x == 0) sigma[blockIdx.x] = nan ? (T)__builtin_nan("") : (T)(r / (T)0.6745);
+    if (threadIdx.x == 0) sigma[blockIdx.x] = (T)(r / (T)0.6745);
 }
 
 }  // namespace

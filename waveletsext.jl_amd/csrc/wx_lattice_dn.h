@@ -46,22 +46,25 @@ namespace {
 
 // HardTH, SoftTH and SemiSoftTH (wx_thresh, wx_common.h) as ONE branch-free rule with wave-uniform parameters: out = v where the rule keeps the
 // coefficient (Hard: not |v| <= t; SemiSoft: |v| > 2 t; Soft: never), else sign(v) max(A |v| - B, 0) with (A, B) = (0, 1) Hard, (1, t) Soft,
-// (2, 2 t) SemiSoft -- A |v| is exact, so the fused multiply-add rounds once like the rule's own subtraction.  (A switch around four copies of the
-// 64 updates spilled 198 registers, a branch per register 22, Hard against the rest 40.  SteinTH keeps the separate kernels.)
+// (2, 2 t) SemiSoft -- A |v| is exact (or +Inf where the rule's own 2 |x| overflows), so A |v| - B rounds once like the rule's subtraction.  The
+// product is an ldexp by a wave-uniform exponent, which -ffp-contract=fast does not fuse into the subtraction (a fused 2 |v| - B would not overflow above DBL_MAX / 2).  Hard
+// drops to 0 whatever A |v| - B is: |v| = t = +Inf must give 0 like abs(x) <= t.  (A switch around four copies of the 64 updates spilled 198
+// registers, a branch per register 22, Hard against the rest 40.  SteinTH keeps the separate kernels.)
 __device__ __forceinline__ void dn_threshold(double (&c)[64], double t, int kind, int lane, unsigned zmask, unsigned zval)
 {
     const unsigned lm = (unsigned)lane & zmask;
     const bool hard = kind == 0;
-    const double A = kind == 0 ? 0.0 : (kind == 1 ? 1.0 : 2.0);
+    int E = kind == 2 ? 1 : 0;                          // A |v| = ldexp(|v|, E) (Hard's product is never used); opaque, or the
+    asm volatile("" : "+v"(E));                         // compiler turns ldexp(x, 0 or 1) into x * (1 or 2) and fuses that again
     const double B = kind == 0 ? 1.0 : (kind == 1 ? t : 2.0 * t);
     const double K = kind == 0 ? t : (kind == 1 ? __builtin_inf() : 2.0 * t);
     lat_for<64>([&](auto Rc) {
         constexpr int r = Rc;
         const unsigned im = lm | ((unsigned)(r << 6) & zmask);
         const double v = c[r], av = fabs(v);
-        const double lin = __builtin_fma(A, av, -B);
+        const double lin = __builtin_ldexp(av, E) - B;
         const double sg = v > 0.0 ? 1.0 : (v < 0.0 ? -1.0 : v);
-        const double sh = lin < 0.0 ? 0.0 : sg * lin;
+        const double sh = (lin < 0.0 || hard) ? 0.0 : sg * lin;
         const bool keep = hard ? !(av <= K) : (av > K);
         const double o = keep ? v : sh;
         c[r] = im == zval ? v : o;

@@ -26,6 +26,15 @@ template <int N, typename F> __device__ __forceinline__ void dn_for(F &&f)
     dn_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
+// Statistics.median!'s middle(a, b) = a/2 + b/2 in T, each half rounded on its own: a subnormal half is inexact, and -ffp-contract=fast fuses
+// a * 0.5 into the addition (one rounding instead of two).  ldexp halves the same way (v_ldexp, correctly rounded) and is not fused; an opaque
+// copy of the halves cost the workgroup counting kernel a wave of occupancy.  For normal values the halves are exact and nothing changes.
+template <typename T> __device__ __forceinline__ T dn_middle(T a, T b)
+{
+    if constexpr (sizeof(T) == 4) return __builtin_ldexpf(a, -1) + __builtin_ldexpf(b, -1);
+    else return __builtin_ldexp(a, -1) + __builtin_ldexp(b, -1);
+}
+
 // order-preserving image of the doubles (NaN aside): a < b <=> key(a) < key(b), -0 just below +0
 __device__ __forceinline__ unsigned long long dn_key(double d)
 {
@@ -36,10 +45,11 @@ __device__ __forceinline__ double dn_unkey(unsigned long long k)
 {
     return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
 }
-// the smallest double above a (finite a)
+// the smallest double above a; +Inf (and NaN) give +Inf, the top of a bracket that stands above every value (dn_median)
 __device__ __forceinline__ double dn_next_up(double a)
 {
     if (a == 0.0) return __longlong_as_double(1ll);
+    if (!(a < __builtin_inf())) return __builtin_inf();
     return dn_unkey(dn_key(a) + 1ull);
 }
 // the value of lane ^ 32 beside the lane's own, as (value of the lower half's lane, value of the upper half's lane): v_permlane32_swap, no LDS
@@ -150,7 +160,9 @@ template <int CB, int NR, typename F> __device__ __forceinline__ void dn_each(F 
 constexpr int dn_nc(int cb) { return cb < 0 ? 1 : 1 << cb; }
 
 // median (Statistics.median!: a/2 + b/2 of the order statistics k and k + 1, cnt even) of v = e (DEV = false) or |e - ctr| (DEV = true) per class
-// and lane group; [blo, bhi): #{v < blo} = 0, #{v < bhi} = cnt
+// and lane group; [blo, bhi): #{v < blo} = 0, #{v < bhi} = cnt -- or bhi = +Inf when the largest value is +Inf (no double lies above it): the
+// bracket's top then counts as cnt, the pivots stay finite (the middle of lo and +Inf is +Inf, so the integer images take over), and when every
+// finite value ranks below k the search ends at lo = DBL_MAX and the final step below finds order statistics k and k + 1 to be +Inf
 template <int CB, int GW, int ST, bool DEV, int NR = 64, typename T = double, int BW = 1>
 __device__ __forceinline__ void dn_median(const double (&e)[NR], const double (&ctr)[dn_nc(CB)], const double (&blo)[dn_nc(CB)],
                                           const double (&bhi)[dn_nc(CB)], int cnt, bool act, double (&med)[dn_nc(CB)])
@@ -276,8 +288,9 @@ __device__ __forceinline__ void dn_median(const double (&e)[NR], const double (&
     for (int q = 0; q < NC; ++q) {
         const int leq = dn_block_sum<BW>(dn_fin<GW, ST>(le[q]));
         const double nmin = dn_block_ext<BW, false>(dn_gmin<GW, ST>(nx[q]));
+        const double ak = leq >= k + 1 ? a[q] : nmin;           // below rank k only after a bracket topped by +Inf (above): then both are +Inf
         const double b = leq >= k + 2 ? a[q] : nmin;
-        med[q] = (double)(T)((T)((T)a[q] / (T)2) + (T)((T)b / (T)2));
+        med[q] = (double)dn_middle<T>((T)ak, (T)b);
     }
 }
 
@@ -307,17 +320,19 @@ __device__ __forceinline__ void dn_noisest(const double (&e)[NR], double (&sig)[
     for (int q = 0; q < NC; ++q) {
         vmin[q] = dn_block_ext<BW, false>(dn_gmin<GW, ST>(vmin[q])); vmax[q] = dn_block_ext<BW, true>(dn_gmax<GW, ST>(vmax[q]));
         bad[q] = dn_block_sum<BW>(dn_fin<GW, ST>(bad[q]));
-        hi0[q] = dn_next_up(vmax[q]);
+        hi0[q] = dn_next_up(vmax[q]);                                   // +Inf stays +Inf (dn_median)
     }
     dn_median<CB, GW, ST, false, NR, T, BW>(e, zero, vmin, hi0, cnt, act, med);
 #pragma unroll
     for (int q = 0; q < NC; ++q) {
         const double d0 = (double)(T)fabs((double)(T)((T)vmin[q] - (T)med[q])), d1 = (double)(T)fabs((double)(T)((T)vmax[q] - (T)med[q]));
-        dhi[q] = dn_next_up(d0 > d1 ? d0 : d1);
+        dhi[q] = dn_next_up(d0 > d1 ? d0 : d1);                         // an infinite value, or a deviation that overflows T: +Inf
     }
     dn_median<CB, GW, ST, true, NR, T, BW>(e, med, zero, dhi, cnt, act, mad);
+    // NaN among the values, or a median of +-Inf or NaN (half the values one infinity, or middle(-Inf, Inf)): then |v - med| holds NaN
+    // (Inf - Inf), and Statistics.median! of the deviations is NaN -- the counting would just rank around it
 #pragma unroll
-    for (int q = 0; q < NC; ++q) sig[q] = bad[q] ? __builtin_nan("") : (double)(T)((T)mad[q] / (T)0.6745);
+    for (int q = 0; q < NC; ++q) sig[q] = (bad[q] || !(fabs(med[q]) < __builtin_inf())) ? __builtin_nan("") : (double)(T)((T)mad[q] / (T)0.6745);
 }
 
 }  // namespace
