@@ -34,9 +34,9 @@
  *  - Device arrays should start on a 32-byte boundary (what hipMalloc, CuArray-style allocators and whole columns of dyadic length
  *    give); a device pointer that does not -- a view shifted by a few elements -- is taken through an aligned scratch copy on the
  *    call's stream: correct, two device-to-device copies slower.
- *  - Dispatch does not depend on the environment: the library's WX_* tuning knobs (profiles/NOTES.md, DESIGN.md
- *    section 10) are read only when the process also sets WX_KNOBS=1.  The parity suite's dispatch override lives in
- *    csrc/wx_debug.h, outside this header.
+ *  - Dispatch does not depend on the environment: the library's six WX_* test hooks are read
+ *    only when the process also sets WX_KNOBS=1.  The parity suite's dispatch override lives in csrc/wx_debug.h,
+ *    outside this header.
  */
 #ifndef WAVELETSEXT_HIP_H
 #define WAVELETSEXT_HIP_H

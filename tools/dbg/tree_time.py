@@ -1,5 +1,5 @@
 """Tree-driven wptall / iwptall (Float64) on the lattice: random trees, the dwt pyramid, against the fused LDS kernels.
-usage: python tools/dbg/tree_time.py [n] [wavelet]   (WX_LATTICE_TREE=0 selects the round-2 path)"""
+usage: python tools/dbg/tree_time.py [n] [wavelet]"""
 import sys, os
 sys.path.insert(0, os.getcwd())
 import numpy as np

@@ -285,8 +285,7 @@ void k_acwpd_subtree_mfma(const double *__restrict__ top, double *__restrict__ s
 // the MFMA subtree kernel takes the full-depth case: n' = n / 2^D0 = 32 samples, 5 levels below D0
 bool wx_acwpd_mfma_ok(int64_t n, int L, int D0)
 {
-    static const bool off = wx_getenv("WX_ACWPD_MFMA") && atoi(wx_getenv("WX_ACWPD_MFMA")) == 0;
-    if (off || D0 < 0 || D0 > 12 || (n >> D0) != 32 || L - D0 != 5) return false;
+    if (D0 < 0 || D0 > 12 || (n >> D0) != 32 || L - D0 != 5) return false;
     // a block's eight signals are addressed with 32-bit byte offsets from a uniform base
     const int64_t sig_stride = n * ((((int64_t)1) << (D0 + 1)) - 1);
     return 8 * 8 * sig_stride < ((int64_t)1 << 32);
@@ -366,15 +365,10 @@ int wx_dev_acwpd_subtree_mfma(const double *top, double *sum, double *sumsq, int
     tabh[31] = ac.c1;
     const double *tab = (const double *)wx_const_upload(tabh, sizeof tabh, st, true);
     if (!tab) return WX_EHIP;
-    static const int wpe = wx_getenv("WX_ACWPD_MFMA_WPE") ? atoi(wx_getenv("WX_ACWPD_MFMA_WPE")) : 2;
     const unsigned grid = 1u << (2 * D0);
     const int ncols_top = (1 << (D0 + 1)) - 1;
     const size_t lds = (256 * 8 + 48) * sizeof(double);
-    if (wpe == 1 && sums)
-        hipLaunchKernelGGL((k_acwpd_subtree_mfma<1, true>), dim3(grid), dim3(64), lds, st, top, sum, sumsq, tab, D0, ncols_top, batch, accumulate);
-    else if (wpe == 1)
-        hipLaunchKernelGGL((k_acwpd_subtree_mfma<1, false>), dim3(grid), dim3(64), lds, st, top, sum, sumsq, tab, D0, ncols_top, batch, accumulate);
-    else if (sums)
+    if (sums)
         hipLaunchKernelGGL((k_acwpd_subtree_mfma<2, true>), dim3(grid), dim3(64), lds, st, top, sum, sumsq, tab, D0, ncols_top, batch, accumulate);
     else
         hipLaunchKernelGGL((k_acwpd_subtree_mfma<2, false>), dim3(grid), dim3(64), lds, st, top, sum, sumsq, tab, D0, ncols_top, batch, accumulate);

@@ -159,8 +159,7 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
     const int force = wx_force_generic();
     // Float32 FULL trees of 128 / 256 samples: the masked tree kernels in Float32 arithmetic on pairs of signals (wx_lattice_tree_s.h) beat the
     // interleaved full-tree kernels (256 samples: depth 1 0.53 -> 0.41 ms per GiB, depth 8 0.55 -> 0.46): taken as a tree of ones
-    static const bool f32tree_off = wx_getenv("WX_TREES32_FULL") && atoi(wx_getenv("WX_TREES32_FULL")) == 0;
-    const bool f32_full_as_tree = sizeof(T) == 4 && !f32tree_off && tr.full && (n == 256 || (n == 128 && tr.Leff >= 2)) && F <= 8 && tr.Leff >= 1;   // (128 samples, depth 1: 0.38 against 0.41)
+    const bool f32_full_as_tree = sizeof(T) == 4 && tr.full && (n == 256 || (n == 128 && tr.Leff >= 2)) && F <= 8 && tr.Leff >= 1;   // (128 samples, depth 1: 0.38 against 0.41)
     if constexpr (sizeof(T) == 4) {
         // Float32 full trees of 64 .. 2048 samples: the interleaved lattice kernels where they apply (wx_lattice_sg32.h)
         if (small && tr.full && !f32_full_as_tree && tr.Leff >= 1 && batch && dx != dy && !wx_skip_register_kernels()) {
@@ -193,8 +192,7 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
         if (r) return io.finish(r < 0 ? r : WX_OK);
     }
     if (small && tr.Leff >= 1 && batch && dx != dy) {
-        static const bool lane_off = wx_getenv("WX_LANETREE") && atoi(wx_getenv("WX_LANETREE")) == 0;
-        if (!lane_off && (n <= 64 || (n <= 128 && sizeof(T) == 4))) {
+        if ((n <= 64 || (n <= 128 && sizeof(T) == 4))) {
             // one lane per signal: the tree as a bit mask (at most 255 nodes of depth < Leff)
             WxLaneTree lt;
             memset(&lt, 0, sizeof lt);
@@ -350,8 +348,7 @@ static int api_denoiseall_sig(const T *x, T *y, int64_t n, int L, int64_t batch,
     if (batch && (!dx || !dy || (sigma && !dsig))) return io.finish(WX_EHIP);
     if (batch == 0) return io.finish(WX_OK);
     if constexpr (sizeof(T) == 8) {
-        static const bool off = wx_getenv("WX_DENOISE_ONEPASS") && atoi(wx_getenv("WX_DENOISE_ONEPASS")) == 0;
-        if (!off && !wx_force_generic() && !wx_skip_register_kernels() && th_kind != 3 && L >= 1 && wx_lattice_applicable_f64(filt)) {
+        if (!wx_force_generic() && !wx_skip_register_kernels() && th_kind != 3 && L >= 1 && wx_lattice_applicable_f64(filt)) {
             int r = 0;
             switch (n) {
 #define WX_DN_CASE(k) case 4096 >> k: r = wx_lattice_denoise##k##_f64(dx, dy, n, L, batch, filt, th_kind, tscale, undersmooth, dsig, COEFS ? 1 : 0, st); break;

@@ -118,7 +118,7 @@ static int api_wpd2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batc
     T *dy = (T *)io.out(y, sizeof(T) * m * n * (L + 1) * batch);
     if (batch && (!dx || !dy)) return io.finish(WX_EHIP);
     // 64 x 64 images: the image read once, every slice written once (wx_lattice_2d64w.hip)
-    if (m == 64 && n == 64 && L >= 1 && batch > 0 && !wx_force_generic() && !wx_getenv("WX_NO_2D64W")) {
+    if (m == 64 && n == 64 && L >= 1 && batch > 0 && !wx_force_generic()) {
         const int r = wx_lattice_2d64_wpd(dx, dy, L, batch, filt, st);
         if (r) return io.finish(r < 0 ? r : WX_OK);
     }
@@ -149,7 +149,7 @@ static int api_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, const uint8_
     // 64 x 64 images along a quad tree whose root is split: the whole tree in the registers of one wavefront (wx_lattice_2d64t.h) --
     // pyramids included (with the policy below)
     const bool q64 = tree && !wx_force_generic() && m == 64 && n == 64 && batch > 0 && ntree >= 1 && tree[0] && F >= 2 && F <= 16 && !(F & 1) &&
-                     x != y && !wx_getenv("WX_NO_2D64T");
+                     x != y;
     if (tree && !wx_force_generic()) {
         const int Ld = wx_tree_depth2d(tree, ntree);
         std::vector<uint8_t> chain((size_t)ntree, 0);
@@ -189,7 +189,7 @@ static int api_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, const uint8_
         }
     }
     // 64 x 64 images: the whole quad tree in the registers of one wavefront, one pass (wx_lattice_2d64.h)
-    if (tr.full && tr.Leff > 0 && !tail && m == 64 && n == 64 && batch && !wx_force_generic() && !wx_getenv("WX_NO_2D64")) {
+    if (tr.full && tr.Leff > 0 && !tail && m == 64 && n == 64 && batch && !wx_force_generic()) {
         const int r = wx_lattice_2d64(INVERSE, dx, dy, tr.Leff, batch, m * n, filt, st);
         if (r) return io.finish(r < 0 ? r : WX_OK);
     }
@@ -246,7 +246,7 @@ static int api_iwpd2d(const T *xw, T *xh, int64_t m, int64_t n, int k, int L, co
     T *dxh = (T *)io.out(xh, sizeof(T) * mn * batch);
     if (batch && (!dxw || !dxh)) return io.finish(WX_EHIP);
     T *tmp = nullptr, *pong = nullptr, *leaves = nullptr;
-    if (tr.full && tr.Leff > 0 && m == 64 && n == 64 && batch && !wx_force_generic() && !wx_getenv("WX_NO_2D64")) {
+    if (tr.full && tr.Leff > 0 && m == 64 && n == 64 && batch && !wx_force_generic()) {
         const int r = wx_lattice_2d64(true, dxw + (int64_t)tr.Leff * mn, dxh, tr.Leff, batch, mn * k, filt, st);
         if (r) return io.finish(r < 0 ? r : WX_OK);
     }

@@ -325,8 +325,6 @@ static int api_acwpd_jbb_moments(const double *x, double *sum, double *sumsq, in
         const int64_t ncols_top = ((int64_t)1 << (D0 + 1)) - 1;
         const int64_t nk_top = n * ncols_top;
         int64_t chunk = ((int64_t)8 << 30) / (int64_t)(sizeof(double) * nk_top);
-        static const int64_t chunk_env = wx_getenv("WX_ACWPD_CHUNK") ? atoll(wx_getenv("WX_ACWPD_CHUNK")) : 0;   // signals per pass (experiment: table in the Infinity Cache)
-        if (chunk_env > 0 && chunk_env < chunk) chunk = chunk_env;
         if (chunk < 1) chunk = 1;
         if (chunk > batch) chunk = batch;
         double *tab = batch ? (double *)scr.alloc(sizeof(double) * nk_top * chunk) : nullptr;
@@ -336,8 +334,7 @@ static int api_acwpd_jbb_moments(const double *x, double *sum, double *sumsq, in
         // moment kernels, which are bound by FP64 issue.  Rounding differs from the reference's sequential sum(X, dims=3)
         // (bestbasis_tree.jl:153) by the association only; identical signals in a power-of-two batch still give sigma = 0 exactly
         // (scaling by 2^k commutes with every rounding of the transform).
-        static const bool lin_off = wx_getenv("WX_ACWPD_LINSUM") && atoi(wx_getenv("WX_ACWPD_LINSUM")) == 0;
-        const bool linear = !lin_off && batch > 0 && D0 > 0 && wx_acwpd_top_moments_ok(n, D0) && wx_acwpd_mfma_ok(n, L, D0);
+        const bool linear = batch > 0 && D0 > 0 && wx_acwpd_top_moments_ok(n, D0) && wx_acwpd_mfma_ok(n, L, D0);
         if (linear) {
             const int groups = 64;
             double *part = (double *)scr.alloc(sizeof(double) * n * (groups + 1));

@@ -452,8 +452,7 @@ int api_bb_costs(const T *X, T *costs, int64_t m, int64_t n, int64_t k, int64_t 
     if (!dX || !dc) return io.finish(WX_EHIP);
     T *dn = (T *)scr.alloc(sizeof(T) * batch);
     if (!dn) return io.finish(WX_EHIP);
-    static const bool wave_off = wx_getenv("WX_BB_WAVE") && atoi(wx_getenv("WX_BB_WAVE")) == 0;
-    if (!two_d && !redundant && !wave_off && (m == 64 || m == 128 || m == 256 || m == 512) && batch <= 0x7ffffff0) {
+    if (!two_d && !redundant && (m == 64 || m == 128 || m == 256 || m == 512) && batch <= 0x7ffffff0) {
         const dim3 g((unsigned)((batch + 3) / 4));
         switch (m) {
         case 64: hipLaunchKernelGGL((k_bb_costs1d_wave<T, 1, true>), g, dim3(256), 0, st, dX, (int)k, cost_kind, ncost, batch, dc); break;
@@ -469,7 +468,7 @@ int api_bb_costs(const T *X, T *costs, int64_t m, int64_t n, int64_t k, int64_t 
         const T *xs = dX + b0 * sigsz * k;
         if (!two_d || redundant)
             hipLaunchKernelGGL(k_bb_norms<T>, dim3((unsigned)bc), dim3(256), 0, st, xs, sigsz, sigsz * k, dn + b0);
-        if (!two_d && !redundant && m <= 256 && m >= 2 && !(m & (m - 1)) && !wx_getenv("WX_BB_SHORT_OFF")) {
+        if (!two_d && !redundant && m <= 256 && m >= 2 && !(m & (m - 1))) {
             int lg = 0;
             while (((int64_t)1 << lg) < m) ++lg;
             const int64_t total = bc * k * m;
@@ -537,8 +536,7 @@ int api_treeselect_batch(T *costs, int64_t ncost, int64_t m, int64_t n, int type
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "tree selection kernel failed to launch"));
         return io.finish(WX_OK);
     }
-    static const bool wave_off = wx_getenv("WX_BB_WAVE") && atoi(wx_getenv("WX_BB_WAVE")) == 0;
-    if (!two_d && !wave_off && ncost <= 511 && batch <= 0x7ffffff0) {      // up to 256 samples (512: 0.125 against 0.109 ms)
+    if (!two_d && ncost <= 511 && batch <= 0x7ffffff0) {      // up to 256 samples (512: 0.125 against 0.109 ms)
         const size_t per = ((size_t)ncost * (sizeof(T) + 1) + 15) & ~(size_t)15;
         hipLaunchKernelGGL(k_bb_treeselect_w<T>, dim3((unsigned)((batch + 3) / 4)), dim3(256), 4 * per, st, dc, ncost, L, ntree, type_max, batch, dt);
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "tree selection kernel failed to launch"));

@@ -563,8 +563,7 @@ int api_noisest(const T *X, int64_t n, int64_t k, int64_t batch, int64_t row_lo,
     const T *dX = (const T *)io.in(X, sizeof(T) * n * k * batch);
     T *ds = (T *)io.out(sigma, sizeof(T) * batch);
     if (!dX || !ds) return io.finish(WX_EHIP);
-    static const int mad_count_wg = wx_getenv("WX_MAD_COUNT_WG") ? atoi(wx_getenv("WX_MAD_COUNT_WG")) : 1;
-    if (mad_count_wg && (cnt == 8192 || cnt == 16384 || cnt == 32768) && batch <= 0x7ffffff0) {
+    if ((cnt == 8192 || cnt == 16384 || cnt == 32768) && batch <= 0x7ffffff0) {
         const dim3 g((unsigned)batch);
         if (cnt == 8192) hipLaunchKernelGGL((k_mad_count_wg<T, 32, 4>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, ds);
         else if (cnt == 16384) hipLaunchKernelGGL((k_mad_count_wg<T, 64, 4>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, ds);
@@ -589,38 +588,26 @@ int api_noisest(const T *X, int64_t n, int64_t k, int64_t batch, int64_t row_lo,
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "noisest kernel failed to launch"));
         return io.finish(WX_OK);
     }
-    // 65 ... 2048 coefficients: one wavefront sorts the values in its registers (k_mad_sort); WX_MAD_SORT_MAX (knob) lowers the limit
-    // (measured per GiB of signals, denoiseall: n = 256 / 512 / 1024 -- 128 / 256 / 512 coefficients -- 3.13 / 4.86 / 3.24 -> 1.83 / 1.88 / 1.83 ms;
-    // 1024 / 2048 coefficients lose to the workgroup selection: 3.5 against 2.3, 4.3 against 1.8 ms -- the cross-lane stages grow with E)
-    static const int mad_sort_max = wx_getenv("WX_MAD_SORT_MAX") ? atoi(wx_getenv("WX_MAD_SORT_MAX")) : 256;
-    // 128 ... 512 coefficients (knobs WX_MAD_ROWS_MIN / WX_MAD_ROWS_MAX; built for 32 ... 1024), a power of two: four signals per wavefront
-    // (k_mad_count_rows).  Per GiB of Float64 signals: 32 / 64 coefficients 1.03 / 0.67 ms against the sorting kernel's 0.55 / 0.69; 128 / 256 / 512
-    // 0.47 / 0.37 / 0.32 against 0.67 (sort) / 0.63 / 0.43 (one signal per wavefront); 1024 0.33 against 0.32
-    static const int mad_rows_max = wx_getenv("WX_MAD_ROWS_MAX") ? atoi(wx_getenv("WX_MAD_ROWS_MAX")) : 512;
-    static const int mad_rows_min = wx_getenv("WX_MAD_ROWS_MIN") ? atoi(wx_getenv("WX_MAD_ROWS_MIN")) : 128;
-    if (cnt >= 32 && cnt >= mad_rows_min && cnt <= 1024 && cnt <= mad_rows_max && (cnt & (cnt - 1)) == 0 && batch <= 0x7ffffff0) {
+    // 128, 256, 512 coefficients: four signals per wavefront (k_mad_count_rows).  Per GiB of Float64 signals: 128 / 256 / 512 coefficients
+    // 0.47 / 0.37 / 0.32 ms against 0.67 (sort) / 0.63 / 0.43 (one signal per wavefront); 32 / 64 coefficients 1.03 / 0.67 ms against the
+    // sorting kernel's 0.55 / 0.69; 1024 0.33 against 0.32
+    if ((cnt == 128 || cnt == 256 || cnt == 512) && batch <= 0x7ffffff0) {
         const dim3 g((unsigned)((batch + 15) / 16));
 #define WX_MR(NRR) hipLaunchKernelGGL((k_mad_count_rows<T, NRR>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, batch, ds)
         switch (cnt) {
-        case 32: WX_MR(2); break;
-        case 64: WX_MR(4); break;
         case 128: WX_MR(8); break;
         case 256: WX_MR(16); break;
-        case 512: WX_MR(32); break;
-        default: WX_MR(64); break;
+        default: WX_MR(32); break;
         }
 #undef WX_MR
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "noisest kernel failed to launch"));
         return io.finish(WX_OK);
     }
-    // 256 ... 4096 coefficients (a power of two): one wavefront per signal counts against pivots (k_mad_count); WX_MAD_COUNT_MIN (knob) moves the lower limit
-    static const int mad_count_min = wx_getenv("WX_MAD_COUNT_MIN") ? atoi(wx_getenv("WX_MAD_COUNT_MIN")) : 256;
-    if (cnt >= 256 && cnt >= mad_count_min && cnt <= 4096 && (cnt & (cnt - 1)) == 0 && batch <= 0x7ffffff0) {
+    // 1024, 2048, 4096 coefficients: one wavefront per signal counts against pivots (k_mad_count)
+    if ((cnt == 1024 || cnt == 2048 || cnt == 4096) && batch <= 0x7ffffff0) {
         const dim3 g((unsigned)((batch + 3) / 4));
 #define WX_MC(NRR) hipLaunchKernelGGL((k_mad_count<T, NRR>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, batch, ds)
         switch (cnt) {
-        case 256: WX_MC(4); break;
-        case 512: WX_MC(8); break;
         case 1024: WX_MC(16); break;
         case 2048: WX_MC(32); break;
         default: WX_MC(64); break;
@@ -629,7 +616,10 @@ int api_noisest(const T *X, int64_t n, int64_t k, int64_t batch, int64_t row_lo,
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "noisest kernel failed to launch"));
         return io.finish(WX_OK);
     }
-    if (cnt >= 3 && cnt <= 2048 && cnt <= mad_sort_max && batch <= 0x7ffffff0) {
+    // 3 ... 256 coefficients: one wavefront sorts the values in its registers (k_mad_sort).  Measured per GiB of signals, denoiseall:
+    // n = 256 / 512 / 1024 -- 128 / 256 / 512 coefficients -- 3.13 / 4.86 / 3.24 -> 1.83 / 1.88 / 1.83 ms; 1024 / 2048 coefficients lose to
+    // the workgroup selection: 3.5 against 2.3, 4.3 against 1.8 ms -- the cross-lane stages grow with E
+    if (cnt >= 3 && cnt <= 256 && batch <= 0x7ffffff0) {
         dim3 g((unsigned)((batch + 3) / 4));
 #define WX_MS(EE) hipLaunchKernelGGL((k_mad_sort<T, EE>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds)
 #define WX_MSS(PLL) do { g = dim3((unsigned)((batch + 4 * (64 / PLL) - 1) / (4 * (64 / PLL)))); hipLaunchKernelGGL((k_mad_sort<T, 1, PLL>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds); } while (0)
@@ -639,22 +629,17 @@ int api_noisest(const T *X, int64_t n, int64_t k, int64_t batch, int64_t row_lo,
         else if (cnt <= 32) WX_MSS(32);
         else if (cnt <= 64) WX_MS(1);
         else if (cnt <= 128) WX_MS(2);
-        else if (cnt <= 256) WX_MS(4);
-        else if (cnt <= 512) WX_MS(8);
-        else if (cnt <= 1024) WX_MS(16);
-        else WX_MS(32);
+        else WX_MS(4);
 #undef WX_MS
 #undef WX_MSS
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "noisest kernel failed to launch"));
         return io.finish(WX_OK);
     }
-    static const int mad_wave_max = wx_getenv("WX_MAD_WAVE_MAX") ? atoi(wx_getenv("WX_MAD_WAVE_MAX")) : 128;   // 512 coefficients: 8.7 against 3.2 ms (the counting is quadratic)
-    if (cnt <= 512 && cnt <= mad_wave_max && batch <= 0x7ffffff0) {
+    // one or two coefficients: one wavefront counts for four signals (k_mad_wave; its counting is quadratic: 512 coefficients 8.7 against
+    // 3.2 ms for k_mad)
+    if (cnt < 3 && batch <= 0x7ffffff0) {
         const dim3 g((unsigned)((batch + 3) / 4));
-        if (cnt <= 64) hipLaunchKernelGGL((k_mad_wave<T, 1>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds);
-        else if (cnt <= 128) hipLaunchKernelGGL((k_mad_wave<T, 2>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds);
-        else if (cnt <= 256) hipLaunchKernelGGL((k_mad_wave<T, 4>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds);
-        else hipLaunchKernelGGL((k_mad_wave<T, 8>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds);
+        hipLaunchKernelGGL((k_mad_wave<T, 1>), g, dim3(256), 0, st, dX, n * k, col * n + row_lo, (int)cnt, batch, ds);
         if (hipGetLastError() != hipSuccess) return io.finish(wx_set_error(WX_EHIP, "noisest kernel failed to launch"));
         return io.finish(WX_OK);
     }

@@ -56,11 +56,6 @@ static const uint8_t *wx_full_tree_ones(hipStream_t st)
     static const struct Ones { uint8_t b[4096]; Ones() { memset(b, 1, sizeof b); } } ones;
     return (const uint8_t *)wx_const_upload(ones.b, sizeof ones.b, st, true);
 }
-static bool wx_full_as_tree()
-{
-    static const bool off = wx_getenv("WX_FULL_AS_TREE") && atoi(wx_getenv("WX_FULL_AS_TREE")) == 0;
-    return !off;
-}
 
 // ------------------------------------------------------------------------------------------
 // generic (one level per launch)
@@ -1094,20 +1089,13 @@ static int wx_fused_grid(size_t lds, int64_t batch, int nt)
     return (int)g;
 }
 
-// threads per workgroup of the fused kernels: one lane per 4-output item of a level, capped by
-// WX_FUSED_NT (tuning knob, default 512: measured best on MI355X)
+// threads per workgroup of the fused kernels: one lane per 4-output item of a level, capped at 512 (measured best on MI355X)
 static int wx_fused_nt(int64_t n)
 {
-    static int cap = 0;
-    if (!cap) {
-        const char *e = wx_getenv("WX_FUSED_NT");
-        cap = e ? atoi(e) : 512;
-        if (cap != 64 && cap != 128 && cap != 256 && cap != 512 && cap != 1024) cap = 512;
-    }
     int64_t want = n / 8;
     int nt = 64;
-    while (nt < cap && nt < want) nt <<= 1;
-    // staging registers: n/4 <= 2*NT below 512 threads (a knob value that is too small is raised), n/4 <= 4*NT above
+    while (nt < 512 && nt < want) nt <<= 1;
+    // staging registers: n/4 <= 2*NT below 512 threads, n/4 <= 4*NT above
     while (nt < 512 && n / 4 > 2 * (int64_t)nt) nt <<= 1;
     while (nt < 1024 && n / 4 > 4 * (int64_t)nt) nt <<= 1;
     return nt;
@@ -1348,8 +1336,7 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     }
     if constexpr (sizeof(T) == 4) {
         // short Float32 signals: the interleaved lattice wpd kernel with Float32 at the two ends (wx_lattice_sgw.hip)
-        static const bool g32w_off = wx_getenv("WX_LATTICE_WPD_G32") && atoi(wx_getenv("WX_LATTICE_WPD_G32")) == 0;
-        if (!force_generic && !wx_skip_register_kernels() && !g32w_off && n <= 128) {        // 256 samples: the fused LDS kernel is as fast (0.47-0.58 against 0.44-0.50)
+        if (!force_generic && !wx_skip_register_kernels() && n <= 128) {        // 256 samples: the fused LDS kernel is as fast (0.47-0.58 against 0.44-0.50)
             const int r = wx_lattice_wpd_g_f32((const float *)x, (float *)y, n, L, batch, filt, st);
             if (r) return r < 0 ? r : WX_OK;
         }
@@ -1367,9 +1354,8 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     // the top levels (at most four: signals up to 16 x the longest fused node): ONE tiled pass writes slices 0 .. dtop -- the signal is
     // read once (round 5; until then slice 0 was a copy and every top level read the slice above it: per level a read and a write)
     const int dtop = d0 < L ? d0 : L;
-    static const bool topwpd_off = wx_getenv("WX_TOPTILE_WPD") && atoi(wx_getenv("WX_TOPTILE_WPD")) == 0;
     bool top_done = false;
-    if (!force_generic && !topwpd_off && dtop >= 1 && dtop <= 4 && wx_is_pow2(n) && n >= 8192 && wx_top_levels_ok(filt.F) && x != y) {
+    if (!force_generic && dtop >= 1 && dtop <= 4 && wx_is_pow2(n) && n >= 8192 && wx_top_levels_ok(filt.F) && x != y) {
         const int rc = wx_dev_top_levels_wpd<T>(x, y, n, dtop, batch, n, ys, n, filt, st);
         if (rc) return rc;
         top_done = true;
@@ -1413,9 +1399,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     if constexpr (sizeof(T) == 4) {
         // Float32 full trees of 128 / 256 samples (the columns of 128- / 256-row images arrive here too): the masked tree kernels in Float32
         // arithmetic on pairs of signals, as a tree of ones (wx_lattice_tree_s.h; policy and numbers: api_wpt1d)
-        static const bool f32tree_off = wx_getenv("WX_TREES32_FULL") && atoi(wx_getenv("WX_TREES32_FULL")) == 0;
-        static const bool f32tree_big = wx_getenv("WX_TREES32_FULL") && atoi(wx_getenv("WX_TREES32_FULL")) == 2;
-        if (!force_generic && !noreg && !status && !f32tree_off && (n == 256 || (n == 128 && L >= 2) || (f32tree_big && n >= 1024 && n <= 4096)) && filt.F <= 8 && x != y && batch >= 2 * 4096 / n) {
+        if (!force_generic && !noreg && !status && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && x != y && batch >= 2 * 4096 / n) {
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
                 const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st);
@@ -1535,7 +1519,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
             if (r) return r < 0 ? r : WX_OK;
         }
         // a full tree nothing above took, as a tree
-        if (!force_generic && !noreg && !status && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 && wx_full_as_tree() &&
+        if (!force_generic && !noreg && !status && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 &&
             wx_lattice_tree_applicable_T<T>(n, filt)) {
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
@@ -1597,9 +1581,8 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
 // (8192 Float64 / 16384 Float32 samples)
 template <typename T> static int64_t wx_dwt_long_plan(int64_t n, const WxFilt &filt, bool *lattice)
 {
-    static const bool off = wx_getenv("WX_DWT_LONG") && atoi(wx_getenv("WX_DWT_LONG")) == 0;
     *lattice = false;
-    if (off || !wx_is_pow2(n) || n > ((int64_t)1 << 24)) return 0;
+    if (!wx_is_pow2(n) || n > ((int64_t)1 << 24)) return 0;
     // 8192 samples (and, Float32, 16384) fit the fused LDS kernel, but one top pass + the lattice pyramid on the approximation
     // moves 3 n samples at memory speed (Float64 8192 samples: 1.38 -> 1.2 ms per 2 GiB)
     if (n >= 8192 && wx_top_levels_ok(filt.F) && !wx_skip_register_kernels() && wx_lattice_tree_applicable_T<T>(4096, filt)) {
@@ -1792,8 +1775,8 @@ template int wx_dev_idwt_long<float>(const float *, float *, int64_t, int, int64
 template <typename T> bool wx_wpt_long_tree_ok(int64_t n, const WxFilt &filt)
 {
     bool lattice;
-    static const int64_t minn = wx_getenv("WX_LONG_TREE_MINN") ? atoll(wx_getenv("WX_LONG_TREE_MINN")) : 8192;     // 8192: random trees 0.30 / 0.22 -> 0.40 / 0.39 of the HBM peak against the fused LDS kernel
-    return n >= minn && wx_dwt_long_plan<T>(n, filt, &lattice) == 4096 && lattice && n <= 65536;
+    // from 8192 samples on: random trees 0.30 / 0.22 -> 0.40 / 0.39 of the HBM peak against the fused LDS kernel
+    return n >= 8192 && wx_dwt_long_plan<T>(n, filt, &lattice) == 4096 && lattice && n <= 65536;
 }
 template bool wx_wpt_long_tree_ok<double>(int64_t, const WxFilt &);
 template bool wx_wpt_long_tree_ok<float>(int64_t, const WxFilt &);
@@ -2000,9 +1983,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
         }
     }
     if constexpr (sizeof(T) == 4) {
-        static const bool f32tree_off = wx_getenv("WX_TREES32_FULL") && atoi(wx_getenv("WX_TREES32_FULL")) == 0;
-        static const bool f32tree_big = wx_getenv("WX_TREES32_FULL") && atoi(wx_getenv("WX_TREES32_FULL")) == 2;
-        if (!force_generic && !noreg && !status && !colmap && !f32tree_off && (n == 256 || (n == 128 && L >= 2) || (f32tree_big && n >= 1024 && n <= 4096)) && filt.F <= 8 && xw != xh &&
+        if (!force_generic && !noreg && !status && !colmap && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && xw != xh &&
             batch >= 2 * 4096 / n) {
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
@@ -2109,7 +2090,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
                                               nstatus, st);
             if (r) return r < 0 ? r : WX_OK;
         }
-        if (!force_generic && !noreg && !status && !colmap && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 && wx_full_as_tree() &&
+        if (!force_generic && !noreg && !status && !colmap && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 &&
             wx_lattice_tree_applicable_T<T>(n, filt)) {
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {

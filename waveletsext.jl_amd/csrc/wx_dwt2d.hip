@@ -483,22 +483,16 @@ template <typename T> static void wx_rows_geometry(int64_t n, int &R, int &S)
 {
     // Strips of 256 bytes per column (64 Float32 / 32 Float64 rows) where the two LDS images fit, halved until they do; low strips get a
     // quarter of padding on the pitch when that still fits (bank conflicts between the columns of a window).  Measured in round 4
-    // (tools/dbg/rows_sweep.sh, full depth, ms per GiB fwd / inv): Float64 256 columns (16, 24) 1.00 / 0.94 -> (32, 32) 0.83 / 0.79; Float32
+    // (profiles/r04_rows_sweep.txt, full depth, ms per GiB fwd / inv): Float64 256 columns (16, 24) 1.00 / 0.94 -> (32, 32) 0.83 / 0.79; Float32
     // 64 columns (32, 32) 1.02 / 0.94 -> (64, 64) 0.83 / 0.77; Float32 1024 columns (16, 16) 1.67 / 1.14 -> (16, 20) 1.34 / 1.18.
     constexpr int VW = 16 / (int)sizeof(T);
     R = 256 / (int)sizeof(T);
     S = R;
-    // tuning knobs (strip height, a power of two, and LDS column pitch >= R)
-    const char *er = wx_getenv("WX_ROWS_R"), *es = wx_getenv("WX_ROWS_S");
-    if (er && es) {
-        const int r = atoi(er), s2 = atoi(es);
-        if (r >= 4 && r <= 64 && (r & (r - 1)) == 0 && s2 >= r && s2 <= 128) { R = r; S = s2; }
-    }
     while (R > VW && (size_t)2 * n * S * sizeof(T) > 160 * 1024) {
         R >>= 1;
         S = R;
     }
-    if (!(er && es) && R <= 16 && R >= 8 && (size_t)2 * n * (R + R / 4) * sizeof(T) <= 160 * 1024 && (R + R / 4) % VW == 0)
+    if (R <= 16 && R >= 8 && (size_t)2 * n * (R + R / 4) * sizeof(T) <= 160 * 1024 && (R + R / 4) % VW == 0)
         S = R + R / 4;
 }
 
@@ -515,8 +509,7 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
                           int64_t batch, const WxFilt &filt, hipStream_t st)
 {
     // images of 128, 256, 512 columns: the rows of a wavefront as interleaved signals of the lattice kernels (wx_lattice_rows.h)
-    static const bool latrows = !(wx_getenv("WX_LATROWS") && atoi(wx_getenv("WX_LATROWS")) == 0);
-    if (latrows && batch > 0) {
+    if (batch > 0) {
         const int r = wx_lattice_rows(INVERSE, src, dst, src_img, dst_img, m, n, L, batch, filt, st);
         if (r) return r < 0 ? r : WX_OK;
     }
@@ -526,19 +519,15 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     // 16-byte row vectors when the geometry and the pointers allow it
     constexpr int VW = 16 / (int)sizeof(T);
     const bool vec = m % VW == 0 && R % VW == 0 && S % VW == 0 && src_img % VW == 0 && dst_img % VW == 0 &&
-                     ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && filt.F <= 12 &&   // 2F-tap window of vectors in registers
-                     !wx_getenv("WX_ROWS_SCALAR");
+                     ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && filt.F <= 12;     // 2F-tap window of vectors in registers
     void (*kern)(const T *, T *, int64_t, int64_t, int, int, int, int64_t, WxFilt, int, int, int, int) = nullptr;
-    static const int xcd_env = wx_getenv("WX_ROWS_XCD") ? atoi(wx_getenv("WX_ROWS_XCD")) : 1;
-    static const int regl_env = wx_getenv("WX_ROWS_REGL") ? atoi(wx_getenv("WX_ROWS_REGL")) : 1;
     // in place (one LDS image, two workgroups of 1024 lanes per CU) when a lane has at most two items per level
-    static const int inplace_env = wx_getenv("WX_ROWS_INPLACE") ? atoi(wx_getenv("WX_ROWS_INPLACE")) : 1;
     // (two workgroups of 512 lanes: the same 16 wavefronts per CU as one workgroup of 1024 with two LDS images,
     // but their load / compute / store phases interleave)
     const int nt_ip = 512;
     const int lanes_per_col = vec ? R / VW : R;
     const int items_per_lane = (int)((n / 4 + (nt_ip / lanes_per_col) - 1) / (nt_ip / lanes_per_col));
-    const bool inplace = inplace_env && vec && filt.F <= 8 && lanes_per_col <= nt_ip && items_per_lane <= 2 &&
+    const bool inplace = vec && filt.F <= 8 && lanes_per_col <= nt_ip && items_per_lane <= 2 &&
                          (size_t)n * S * sizeof(T) <= 80 * 1024 && (size_t)n * S * sizeof(T) > 40 * 1024;
     if (inplace) lds = (size_t)n * S * sizeof(T);
     int per_cu = (int)((160 * 1024) / lds);
@@ -546,7 +535,7 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     const int nt = inplace ? nt_ip : (per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024));
     // measured (db4, full depth, 1 GiB): rows of 256 Float64 columns 1.11 -> 0.97 ms, 1024 Float32 columns 1.89 -> 1.65 ms; short rows lose
     // (64 Float32 columns 1.02 -> 1.34 ms, 64 / 128 Float64 columns 1.04 -> 1.39 ms)
-    const bool regl = regl_env && vec && filt.F <= 8 && ((sizeof(T) == 8 && n >= 256) || n >= 1024);
+    const bool regl = vec && filt.F <= 8 && ((sizeof(T) == 8 && n >= 256) || n >= 1024);
     switch (filt.F) {
 #define WX_CASE(FF) case FF: kern = vec ? k_rows_fused<T, FF, INVERSE, VW> : k_rows_fused<T, FF, INVERSE, 1>; break;
         WX_CASE(10) WX_CASE(12) WX_CASE(14) WX_CASE(16) WX_CASE(18) WX_CASE(20)
@@ -572,7 +561,7 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     int log2R = 0;
     while ((1 << (log2R + 1)) <= R) ++log2R;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nt), lds, st, src, dst, src_img, dst_img, (int)m, log2n, L, batch,
-                       filt, log2R, S, xcd_env, regl ? 1 : 0);
+                       filt, log2R, S, 1, regl ? 1 : 0);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
 }
@@ -585,21 +574,15 @@ int wx_dev_wpt2d_fast(const T *x, T *y, int64_t m, int64_t n, int L, int64_t bat
     if (batch == 0 || m * n == 0) return WX_OK;
     const int64_t mn = m * n;
     int rc;
-    // Sub-batches (WX_2D_SUB = images per sub-batch, default 0 = the whole batch per pass): the two passes of S images
-    // run back to back and hand the intermediate image over in a ring of 2 S images of `tmp`, small enough to stay in
-    // the 256 MiB Infinity Cache between its write and its read.  Measured on config 4 (4096 images 512 x 512 Float32):
-    // no gain at any S (forward 6.9 ms whole batch, 6.8 ms at S = 128, 7.7 ms at S = 32) -- the two passes are bound by
-    // latency and LDS issue, not by HBM bandwidth, so halving the HBM traffic does not show; kept as a knob.
-    // Measured again with the lattice column kernels (each pass at ~61 % of HBM peak): step 6.79 ms whole batch, 7.18 ms at
-    // S = 96, 7.74 ms at S = 128, 8.7 ms at S = 64, 11.3 ms at S = 32 -- short launches lose more in ramp-up and tail than
-    // the cache saves.
-    static const int64_t sub_env = wx_getenv("WX_2D_SUB") ? atoll(wx_getenv("WX_2D_SUB")) : 0;
-    int64_t S = sub_env;
-    if (S <= 0 || S >= batch) S = batch;
+    // The whole batch per pass.  Sub-batches of S images, whose intermediate image stays in the 256 MiB Infinity Cache between its write
+    // and its read, were measured on config 4 (4096 images 512 x 512 Float32) and lost: forward 6.9 ms whole batch, 6.8 ms at S = 128,
+    // 7.7 ms at S = 32 -- the two passes are bound by latency and LDS issue, not by HBM bandwidth.  Measured again with the lattice column
+    // kernels (each pass at ~61 % of HBM peak): step 6.79 ms whole batch, 7.18 ms at S = 96, 7.74 ms at S = 128, 8.7 ms at S = 64, 11.3 ms
+    // at S = 32 -- short launches lose more in ramp-up and tail than the cache saves.
     if (!inverse && in_img != mn) return wx_set_error(WX_EUNSUPPORTED, "fast 2-D forward needs a dense input");
     if constexpr (sizeof(T) == 4) {
         // 512 x 512 Float32, depth 6: the transposing lattice kernel applied twice (wx_lattice2d.hip)
-        if (wx_lattice2d_ok(m, n, L, filt, sizeof(T)) && in_img == mn && !(inverse && wx_getenv("WX_LATTICE2D_NOINV"))) {
+        if (wx_lattice2d_ok(m, n, L, filt, sizeof(T)) && in_img == mn) {
             // round 6: both passes in one persistent launch, the intermediate in a ring of <= 128 MiB of `tmp` that stays in the Infinity
             // Cache (k_lat2d_fused_f32).  A launcher that declines (alignment, in-place odd batches of 256 x 256 images) leaves the two
             // launches below.
@@ -631,18 +614,13 @@ int wx_dev_wpt2d_fast(const T *x, T *y, int64_t m, int64_t n, int L, int64_t bat
             }
         }
     }
-    for (int64_t b0 = 0, k = 0; b0 < batch; b0 += S, ++k) {
-        const int64_t nb = (batch - b0 < S) ? batch - b0 : S;
-        T *ring = (S == batch) ? tmp : tmp + (k & 1) * S * mn;
-        if (!inverse) {
-            // columns: the images' columns are m-sample signals, contiguous: (m, n*nb)
-            if ((rc = wx_dev_wpt1d<T>(x + b0 * mn, ring, m, L, n * nb, filt, nullptr, 0, nullptr, st, 0))) return rc;
-            if ((rc = wx_launch_rows<T, false>(ring, y + b0 * mn, mn, mn, m, n, L, nb, filt, st))) return rc;
-        } else {
-            if ((rc = wx_launch_rows<T, true>(x + b0 * in_img, ring, in_img, mn, m, n, L, nb, filt, st))) return rc;
-            if ((rc = wx_dev_iwpt1d<T>(ring, y + b0 * mn, m, L, n * nb, filt, nullptr, 0, nullptr, 0, m, nullptr, nullptr, st, 0)))
-                return rc;
-        }
+    if (!inverse) {
+        // columns: the images' columns are m-sample signals, contiguous: (m, n*batch)
+        if ((rc = wx_dev_wpt1d<T>(x, tmp, m, L, n * batch, filt, nullptr, 0, nullptr, st, 0))) return rc;
+        if ((rc = wx_launch_rows<T, false>(tmp, y, mn, mn, m, n, L, batch, filt, st))) return rc;
+    } else {
+        if ((rc = wx_launch_rows<T, true>(x, tmp, in_img, mn, m, n, L, batch, filt, st))) return rc;
+        if ((rc = wx_dev_iwpt1d<T>(tmp, y, m, L, n * batch, filt, nullptr, 0, nullptr, 0, m, nullptr, nullptr, st, 0))) return rc;
     }
     return WX_OK;
 }
@@ -987,9 +965,8 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
     if (tiles == 0) return true;
     T *di = (T *)tt.dst_int;
     // persistent workgroups with the next tile prefetched (k_dwt2d_level_tile_p): every tile does work (no tree, or the node list)
-    static const int persist = wx_getenv("WX_TILE_PERSIST") ? atoi(wx_getenv("WX_TILE_PERSIST")) : 1;
     constexpr int NBP = ((CR + 2 * H) * (CC + 2 * H) + 255) / 256;
-    if (persist && NBP <= 24 && F <= 10 && (!tt.status || by_node)) {          // (longer filters spill at three wavefronts per SIMD)
+    if (NBP <= 24 && F <= 10 && (!tt.status || by_node)) {          // (longer filters spill at three wavefronts per SIMD)
         auto kp = k_dwt2d_level_tile_p<T, F, CR, CC>;
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -998,8 +975,7 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
         int per_cu = (int)((160 * 1024) / lds);
         if (per_cu < 1) per_cu = 1;
         if (per_cu > 8) per_cu = 8;
-        static const int wgs_env = wx_getenv("WX_TILE_WGS") ? atoi(wx_getenv("WX_TILE_WGS")) : 0;
-        int64_t grid = (int64_t)256 * (wgs_env > 0 ? wgs_env : per_cu);
+        int64_t grid = (int64_t)256 * per_cu;
         if (grid > total) grid = total;
         hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(256), lds, st, src, dst, src_img, dst_img, m, n, d, filt, di, tt.int_img, tt.status,
                            tt.nstatus, by_node ? tt.act : (const int *)nullptr, tiles, total);
@@ -1017,8 +993,6 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
 // true when the level ran as one tile pass; false = not applicable (the caller takes the two-pass level)
 template <typename T> static bool wx_level_tile_ok(int m, int n, int d, int F)
 {
-    static const bool off = wx_getenv("WX_LEVEL2D_TILE") && atoi(wx_getenv("WX_LEVEL2D_TILE")) == 0;
-    if (off) return false;
     const int mp = m >> d, np = n >> d;
     if ((m & (m - 1)) || (n & (n - 1)) || mp < 8 || np < 8) return false;
     if (m % WX_TILE_CR || n % wx_tile_cc<T>()) return false;
@@ -1371,9 +1345,8 @@ static bool wx_launch_ilevel_tile_F(const T *src_leaf, int64_t leaf_img, const T
     const bool by_node = tt.act && mp >= CR && np >= CC;
     const unsigned tiles = by_node ? (unsigned)(tt.nact * (mp / CR) * (np / CC)) : (unsigned)((m / CR) * (n / CC));
     if (tiles == 0) return true;
-    static const int persist = wx_getenv("WX_TILE_PERSIST") ? atoi(wx_getenv("WX_TILE_PERSIST")) : 1;
     constexpr int NBP = (4 * HRm * HCm + 255) / 256;
-    if (persist && NBP <= 24 && F <= 8 && sizeof(T) == 8 && by_node) {          // (Float32: no gain, 1.32 vs 1.34 ms: instruction-bound)     // (Float32 at 8 taps spills 124 bytes per lane at three wavefronts per SIMD: 1.5 -> 1.8 ms)
+    if (NBP <= 24 && F <= 8 && sizeof(T) == 8 && by_node) {          // (Float32: no gain, 1.32 vs 1.34 ms: instruction-bound)     // (Float32 at 8 taps spills 124 bytes per lane at three wavefronts per SIMD: 1.5 -> 1.8 ms)
         auto kp = k_idwt2d_level_tile_p<T, F, CR, CC>;
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1382,8 +1355,7 @@ static bool wx_launch_ilevel_tile_F(const T *src_leaf, int64_t leaf_img, const T
         int per_cu = (int)((160 * 1024) / lds);
         if (per_cu < 1) per_cu = 1;
         if (per_cu > 8) per_cu = 8;
-        static const int wgs_env = wx_getenv("WX_TILE_WGS") ? atoi(wx_getenv("WX_TILE_WGS")) : 0;
-        int64_t grid = (int64_t)256 * (wgs_env > 0 ? wgs_env : per_cu);
+        int64_t grid = (int64_t)256 * per_cu;
         if (grid > total) grid = total;
         hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(256), lds, st, src_leaf, leaf_img, src_int, tt.int_img, dst, dst_img, m, n, d, filt,
                            tt.status, tt.nstatus, tt.act, tiles, total);

@@ -151,9 +151,9 @@ constexpr int hs_revc(int v, int bits)
 // column in dst (dst_cols columns per signal, column = node).  gain = (c / 2)^K.  K = 5: 16 + 16 transform values and
 // 32 running sums per lane leave room for three wavefronts per SIMD (K = 6 needs 258 registers: one wavefront, and the
 // 64 loads of a step are then fully exposed -- measured 16 ms per 32 GiB against 8.5 ms for the LDS passes).
-// ORD (round 6, experiment behind WX_HAAR_ISWT_ORDER): 0 = consecutive blocks are the position groups of one node (the two wavefronts that
-// interleave 512-byte pieces of the same 32 columns run side by side), 1 = consecutive blocks are consecutive nodes (the groups of a node
-// are 2^d0 blocks apart); WPE = wavefronts per SIMD the kernel is built for (0 = the compiler's choice: three)
+// ORD (round 6): 0 = consecutive blocks are the position groups of one node (the two wavefronts that interleave 512-byte pieces of the
+// same 32 columns run side by side), 1 = consecutive blocks are consecutive nodes (the groups of a node are 2^d0 blocks apart; the one
+// launched); WPE = wavefronts per SIMD the kernel is built for (0 = the compiler's choice: three)
 template <int K, int U, int ORD = 0, int WPE = 0>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE ? WPE : 1, WPE ? WPE : 8)))
 void k_haar_iswpt(const double *__restrict__ src, int64_t src_cols,
@@ -226,14 +226,9 @@ void k_haar_iswpt(const double *__restrict__ src, int64_t src_cols,
 
 }  // namespace
 
-static bool hs_enabled()
-{
-    static const bool off = wx_getenv("WX_HAAR_SWT6") && atoi(wx_getenv("WX_HAAR_SWT6")) == 0;
-    return !off;
-}
 bool wx_haar_swpt6_ok(int64_t n, int L, const WxFilt &filt, size_t esz)
 {
-    return hs_enabled() && esz == 8 && filt.F == 2 && filt.q[0] == filt.q[1] && L >= 12 && L <= 30 && (n >> L) >= 1 &&
+    return esz == 8 && filt.F == 2 && filt.q[0] == filt.q[1] && L >= 12 && L <= 30 && (n >> L) >= 1 &&
            ((n >> (L - 6)) % 4) == 0 && (n >> (L - 6)) >= 64;
 }
 
@@ -246,13 +241,7 @@ int wx_haar_swpt6_fwd(double *xw, int64_t n, int L, int64_t batch, const WxFilt 
     const int64_t blocks = ((int64_t)1 << d0) * (((int64_t)1 << d0) >> 6);
     int64_t gy = batch > 65535 ? 65535 : batch;
     // steps per loop iteration: 1 measured best (7.0 ms per 32 GiB; 8.1 at 2, 11.8 at 4: the unrolled bodies spill)
-    static const int U = wx_getenv("WX_HAAR_SWT6_U") ? atoi(wx_getenv("WX_HAAR_SWT6_U")) : 1;
-    if (U == 1)
-        hipLaunchKernelGGL(k_haar_swpt6_fwd<1>, dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, xw, (int)n, 1 << L, batch, d0, gain);
-    else if (U == 2)
-        hipLaunchKernelGGL(k_haar_swpt6_fwd<2>, dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, xw, (int)n, 1 << L, batch, d0, gain);
-    else
-        hipLaunchKernelGGL(k_haar_swpt6_fwd<4>, dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, xw, (int)n, 1 << L, batch, d0, gain);
+    hipLaunchKernelGGL(k_haar_swpt6_fwd<1>, dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, xw, (int)n, 1 << L, batch, d0, gain);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "haar swpt6 launch", __FILE__, __LINE__);
     return WX_OK;
@@ -260,39 +249,20 @@ int wx_haar_swpt6_fwd(double *xw, int64_t n, int L, int64_t batch, const WxFilt 
 
 // depth L -> L - K of the average-based iswpt (K = wx_haar_iswpt_levels()): src (n, src_cols) holds the leaves of the
 // wpt layout, dst gets the 2^(L-K) node columns
-int wx_haar_iswpt_levels()
-{
-    static const int k = wx_getenv("WX_HAAR_ISWT_K") ? atoi(wx_getenv("WX_HAAR_ISWT_K")) : 5;
-    return k == 6 ? 6 : 5;
-}
 int wx_haar_iswpt6(const double *src, int64_t src_cols, double *dst, int64_t dst_cols, int64_t n, int L, int64_t batch,
                    const WxFilt &filt, hipStream_t st)
 {
-    const int K = wx_haar_iswpt_levels();
+    constexpr int K = wx_haar_iswpt_levels();
     const int d0 = L - K;
     double gain = 1.0;
     for (int i = 0; i < K; ++i) gain *= 0.5 * filt.q[0];
     const int64_t blocks = ((int64_t)1 << d0) * (((int64_t)1 << d0) >> 6);
     int64_t gy = batch > 65535 ? 65535 : batch;
-    if (K == 6)
-        hipLaunchKernelGGL((k_haar_iswpt<6, 1>), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, src, src_cols, dst,
-                           dst_cols, (int)n, batch, d0, gain);
-    else
-    {
-        // profiles/r06_cfg3_inverse.txt: six consecutive processes each -- order 1 is 1-2 % faster in every placement of the table (6.88 / 7.47 /
-        // 8.12 ms against 7.03 / 7.58 / 8.19), residency 2 the same as 3, 4 (spills) 18 ms; the spread itself follows the process sequence
-        // whatever the order or the residency: it is the physical placement of the 32 GiB table (profiles/r05_cfg3_inverse.md)
-        static const int ord = wx_getenv("WX_HAAR_ISWT_ORDER") ? atoi(wx_getenv("WX_HAAR_ISWT_ORDER")) : 1;
-        static const int wpe = wx_getenv("WX_HAAR_ISWT_WPE") ? atoi(wx_getenv("WX_HAAR_ISWT_WPE")) : 0;
-#define WX_HI(O, W) hipLaunchKernelGGL((k_haar_iswpt<5, 1, O, W>), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, src, src_cols, dst, dst_cols, (int)n, batch, d0, gain)
-        if (ord == 1 && wpe == 2) WX_HI(1, 2);
-        else if (ord == 1 && wpe == 4) WX_HI(1, 4);
-        else if (ord == 1) WX_HI(1, 0);
-        else if (wpe == 2) WX_HI(0, 2);
-        else if (wpe == 4) WX_HI(0, 4);
-        else WX_HI(0, 0);
-#undef WX_HI
-    }
+    // profiles/r06_cfg3_inverse.txt: six consecutive processes each -- order 1 is 1-2 % faster in every placement of the table (6.88 / 7.47 /
+    // 8.12 ms against 7.03 / 7.58 / 8.19), residency 2 the same as 3, 4 (spills) 18 ms; the spread itself follows the process sequence
+    // whatever the order or the residency: it is the physical placement of the 32 GiB table (profiles/r05_cfg3_inverse.md)
+    hipLaunchKernelGGL((k_haar_iswpt<K, 1, 1, 0>), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, src, src_cols, dst, dst_cols,
+                       (int)n, batch, d0, gain);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "haar iswpt launch", __FILE__, __LINE__);
     return WX_OK;

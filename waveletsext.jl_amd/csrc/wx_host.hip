@@ -303,13 +303,6 @@ void *WxScratch::upload(const void *host, size_t bytes)
 }
 
 // ---- staged IO ----------------------------------------------------------------------------
-#include <chrono>
-static bool wx_host_trace()
-{
-    static const bool on = wx_getenv("WX_HOST_TRACE") && atoi(wx_getenv("WX_HOST_TRACE")) != 0;
-    return on;
-}
-static double wx_now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static hipError_t wx_h2d_staged(void *dev, const void *user, size_t bytes, hipStream_t st);
 static void wx_advise_hugepages(void *user, size_t bytes);
 WxIO::~WxIO()
@@ -345,12 +338,7 @@ const void *WxIO::in(const void *p, size_t bytes)
     if (e != hipSuccess) { wx_set_hip_error(e, "hipMalloc(stage in)", __FILE__, __LINE__); return nullptr; }
     items.push_back({const_cast<void *>(p), d, bytes, true, false, false});
     any_staged = true;
-    const double t0 = wx_host_trace() ? wx_now_ms() : 0.0;
     e = wx_h2d_staged(d, p, bytes, st);
-    if (wx_host_trace()) {
-        (void)hipStreamSynchronize(st);
-        fprintf(stderr, "wx host: H2D %.1f MiB in %.2f ms (%.1f GB/s)\n", bytes / 1048576.0, wx_now_ms() - t0, bytes / (wx_now_ms() - t0) / 1e6);
-    }
     if (e != hipSuccess) { wx_set_hip_error(e, "hipMemcpyAsync(H2D)", __FILE__, __LINE__); return nullptr; }
     return d;
 }
@@ -426,7 +414,7 @@ class WxHostPool {
         std::lock_guard<std::mutex> lk(mu);
         if (started) return;
         started = true;
-        int n = wx_getenv("WX_HOST_THREADS") ? atoi(wx_getenv("WX_HOST_THREADS")) : 16;
+        int n = 16;
         const int hw = (int)std::thread::hardware_concurrency();
         if (hw > 0 && n > hw) n = hw;
         if (n < 1) n = 1;
@@ -506,12 +494,11 @@ void wx_release_host_staging()
 // D2H of a large array into pageable memory through the pinned ring; returns hipSuccess or the first error
 static hipError_t wx_d2h_staged(void *user, const void *dev, size_t bytes, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_HOST_STAGING") && atoi(wx_getenv("WX_HOST_STAGING")) == 0;
     hipPointerAttribute_t at;
     const bool pinned_user = hipPointerGetAttributes(&at, user) == hipSuccess && at.type == hipMemoryTypeHost;
     (void)hipGetLastError();
     std::unique_lock<std::mutex> lk(g_stage_mu, std::try_to_lock);
-    if (off || pinned_user || bytes < ((size_t)8 << 20) || !lk.owns_lock() || !g_ring.init())
+    if (pinned_user || bytes < ((size_t)8 << 20) || !lk.owns_lock() || !g_ring.init())
         return hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, st);
     const size_t CH = WxPinRing::CH;
     const size_t nch = (bytes + CH - 1) / CH;
@@ -567,8 +554,7 @@ extern "C" int wx_set_host_hugepages(int on)
 }
 static void wx_advise_hugepages(void *user, size_t bytes)
 {
-    static const bool off = wx_getenv("WX_HOST_HUGEPAGES") && atoi(wx_getenv("WX_HOST_HUGEPAGES")) == 0;
-    if (off || !g_host_hugepages.load(std::memory_order_relaxed) || bytes < ((size_t)64 << 20)) return;
+    if (!g_host_hugepages.load(std::memory_order_relaxed) || bytes < ((size_t)64 << 20)) return;
     const uintptr_t a = ((uintptr_t)user + ((size_t)2 << 20) - 1) & ~(uintptr_t)(((size_t)2 << 20) - 1);
     const uintptr_t b = ((uintptr_t)user + bytes) & ~(uintptr_t)(((size_t)2 << 20) - 1);
     if (b > a) (void)madvise((void *)a, (size_t)(b - a), MADV_HUGEPAGE);
@@ -580,12 +566,11 @@ static void wx_advise_hugepages(void *user, size_t bytes)
 // ring is free again (the buffers belong to the next staged copy).
 static hipError_t wx_h2d_staged(void *dev, const void *user, size_t bytes, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_HOST_STAGING") && atoi(wx_getenv("WX_HOST_STAGING")) == 0;
     hipPointerAttribute_t at;
     const bool pinned_user = hipPointerGetAttributes(&at, user) == hipSuccess && at.type == hipMemoryTypeHost;
     (void)hipGetLastError();
     std::unique_lock<std::mutex> lk(g_stage_mu, std::try_to_lock);
-    if (off || pinned_user || bytes < ((size_t)64 << 20) || !lk.owns_lock() || !g_ring.init())
+    if (pinned_user || bytes < ((size_t)64 << 20) || !lk.owns_lock() || !g_ring.init())
         return hipMemcpyAsync(dev, user, bytes, hipMemcpyHostToDevice, st);
     const size_t CH = WxPinRing::CH;
     const size_t nch = (bytes + CH - 1) / CH;
@@ -635,13 +620,7 @@ int WxIO::finish(int rc)
     if (rc == WX_OK) {
         for (auto &it : items)
             if (it.copy_out && it.staged) {
-                double t0 = 0.0;
-                if (wx_host_trace()) { (void)hipStreamSynchronize(st); t0 = wx_now_ms(); }
                 hipError_t e = wx_d2h_staged(it.user, it.dev, it.bytes, st);
-                if (wx_host_trace()) {
-                    (void)hipStreamSynchronize(st);
-                    fprintf(stderr, "wx host: D2H %.1f MiB in %.2f ms (%.1f GB/s)\n", it.bytes / 1048576.0, wx_now_ms() - t0, it.bytes / (wx_now_ms() - t0) / 1e6);
-                }
                 if (e != hipSuccess) rc = wx_set_hip_error(e, "hipMemcpyAsync(D2H)", __FILE__, __LINE__);
             }
     }

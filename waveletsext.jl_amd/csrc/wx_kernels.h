@@ -75,7 +75,7 @@ void wx_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, size_t esz
 // last six levels of the Haar swpt / average-based iswpt as sliding Walsh-Hadamard transforms (wx_haarswt.hip)
 bool wx_haar_swpt6_ok(int64_t n, int L, const WxFilt &filt, size_t esz);
 int wx_haar_swpt6_fwd(double *xw, int64_t n, int L, int64_t batch, const WxFilt &filt, hipStream_t st);
-int wx_haar_iswpt_levels();
+static constexpr int wx_haar_iswpt_levels() { return 5; }   // levels of the register pass of the inverse
 int wx_haar_iswpt6(const double *src, int64_t src_cols, double *dst, int64_t dst_cols, int64_t n, int L, int64_t batch,
                    const WxFilt &filt, hipStream_t st);
 template <typename T>

@@ -116,28 +116,21 @@ int wx_lattice_launch_lo(bool inverse, const double *x, double *y, int L, int64_
 static int wx_lattice_launch(bool inverse, const double *x, double *y, int64_t n, int L, int64_t batch, int64_t in_stride,
                              const WxFilt &filt, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0;
-    static const bool off_sh = wx_getenv("WX_LATTICE_SH") && atoi(wx_getenv("WX_LATTICE_SH")) == 0;
-    if (!off && !off_sh && (n == 2048 || n == 1024))
+    if (n == 2048 || n == 1024)
         return wx_lattice_launch_sh(inverse, x, y, n, L, batch, inverse ? in_stride : n, filt, st);
-    if (!off && !off_sh && n >= 64 && n <= 512)
+    if (n >= 64 && n <= 512)
         return wx_lattice_launch_g(inverse, x, y, n, L, batch, inverse ? in_stride : n, filt, st);
-    static const bool off_lo = wx_getenv("WX_LATTICE_LO") && atoi(wx_getenv("WX_LATTICE_LO")) == 0;
-    if (!off && !off_lo && n == 4096 && L >= 1 && L <= 5) return wx_lattice_launch_lo(inverse, x, y, L, batch, inverse ? in_stride : n, filt, st);
-    if (off || n != 4096 || L < 6 || L > 12 || filt.F < 2 || batch <= 0) return 0;
+    if (n == 4096 && L >= 1 && L <= 5) return wx_lattice_launch_lo(inverse, x, y, L, batch, inverse ? in_stride : n, filt, st);
+    if (n != 4096 || L < 6 || L > 12 || filt.F < 2 || batch <= 0) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     if (inverse && (in_stride & 3)) return 0;
     WxLat cf;
     if (!wx_lattice_factor(filt, L, inverse, &cf)) return 0;
-    static const int wg_per_cu = wx_getenv("WX_LATTICE_WG") ? atoi(wx_getenv("WX_LATTICE_WG")) : 0;
     int64_t grid = batch;
-    if (wg_per_cu > 0 && grid > (int64_t)256 * wg_per_cu) grid = (int64_t)256 * wg_per_cu;
     if (grid > 0x7fffffff) grid = 0x7fffffff;
     // wavefronts per SIMD the kernels are compiled for (amdgpu_waves_per_eu): the forward fits 3 (166 registers); the
     // inverse needs 194 registers without spills, and its spills at 3 cost 15 % extra HBM traffic (scratch) and 6 % time
-    // (db4 L = 10: 0.84 ms at 3, 0.78 ms at 2; the forward built for 2 is 2 % slower than for 3).  WX_LATTICE_INV_WPE = 3
-    // selects the other build of the inverse.
-    // (the three-wavefront build of the inverse was reachable through WX_LATTICE_INV_WPE=3 only: not built since round 6)
+    // (db4 L = 10: 0.84 ms at 3, 0.78 ms at 2; the forward built for 2 is 2 % slower than for 3)
 #define WX_GO(NSS)                                                                                                  \
     case NSS:                                                                                                       \
         if (inverse)                                                                                                \
@@ -160,12 +153,9 @@ int wx_lattice_wpd_sh_f64(const double *x, double *y, int64_t n, int L, int64_t 
 
 int wx_lattice_wpd_f64(const double *x, double *y, int64_t n, int L, int64_t batch, const WxFilt &filt, hipStream_t st)
 {
-    static const bool off = (wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0) ||
-                            (wx_getenv("WX_LATTICE_WPD") && atoi(wx_getenv("WX_LATTICE_WPD")) == 0);
-    static const bool off_sh = wx_getenv("WX_LATTICE_SH") && atoi(wx_getenv("WX_LATTICE_SH")) == 0;
-    if (!off && !off_sh && (n == 2048 || n == 1024) && x != (const double *)y) return wx_lattice_wpd_sh_f64(x, y, n, L, batch, filt, st);
-    if (!off && !off_sh && n >= 64 && n <= 512 && x != (const double *)y) return wx_lattice_wpd_g_f64(x, y, n, L, batch, filt, st);
-    if (off || n != 4096 || L < 1 || L > 12 || filt.F < 2 || batch <= 0 || batch > 0x7fffffff) return 0;
+    if ((n == 2048 || n == 1024) && x != (const double *)y) return wx_lattice_wpd_sh_f64(x, y, n, L, batch, filt, st);
+    if (n >= 64 && n <= 512 && x != (const double *)y) return wx_lattice_wpd_g_f64(x, y, n, L, batch, filt, st);
+    if (n != 4096 || L < 1 || L > 12 || filt.F < 2 || batch <= 0 || batch > 0x7fffffff) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     WxLatW cw;
     if (!wx_lattice_factor(filt, L, false, &cw.c)) return 0;
@@ -197,8 +187,7 @@ int wx_lattice_wpd_f64(const double *x, double *y, int64_t n, int L, int64_t bat
 
 bool wx_lattice_applicable_f64(const WxFilt &filt)
 {
-    static const bool off = wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0;
-    if (off || filt.F < 2 || filt.F / 2 > WX_LAT_MAXS) return false;
+    if (filt.F < 2 || filt.F / 2 > WX_LAT_MAXS) return false;
     WxLat tmp;
     return wx_lattice_factor(filt, 6, false, &tmp);
 }
@@ -209,15 +198,13 @@ int wx_lattice_iwpt8k_f64(const double *xw, double *y, int L, int64_t batch, int
 
 int wx_lattice_wpt_f64(const double *x, double *y, int64_t n, int L, int64_t batch, const WxFilt &filt, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0;
-    if (n == 8192 && !off) return wx_lattice_wpt8k_f64(x, y, L, batch, filt, st);
+    if (n == 8192) return wx_lattice_wpt8k_f64(x, y, L, batch, filt, st);
     return wx_lattice_launch(false, x, y, n, L, batch, n, filt, st);
 }
 int wx_lattice_iwpt_f64(const double *xw, double *y, int64_t n, int L, int64_t batch, int64_t in_stride, const WxFilt &filt,
                         hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0;
-    if (n == 8192 && !off) return wx_lattice_iwpt8k_f64(xw, y, L, batch, in_stride, filt, st);
+    if (n == 8192) return wx_lattice_iwpt8k_f64(xw, y, L, batch, in_stride, filt, st);
     return wx_lattice_launch(true, xw, y, n, L, batch, in_stride, filt, st);
 }
 
@@ -236,8 +223,7 @@ WX_TREES_DECL(3f) WX_TREES_DECL(3i) WX_TREES_DECL(4f) WX_TREES_DECL(4i) WX_TREES
 #undef WX_TREES_DECL
 static bool wx_lattice_trees_short(int64_t n, const WxFilt &filt)
 {
-    static const bool off = wx_getenv("WX_LATTICE_TREES") && atoi(wx_getenv("WX_LATTICE_TREES")) == 0;
-    return !off && (n == 512 || n == 256 || n == 128 || n == 64) && filt.F <= 16;
+    return (n == 512 || n == 256 || n == 128 || n == 64) && filt.F <= 16;
 }
 #define WX_TREES_GO(TS)                                                                                                              \
     switch (n) {                                                                                                                     \
@@ -253,9 +239,7 @@ static bool wx_lattice_trees_short(int64_t n, const WxFilt &filt)
 
 bool wx_lattice_tree_applicable_f64(int64_t n, const WxFilt &filt)
 {
-    static const bool off = (wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0) ||
-                            (wx_getenv("WX_LATTICE_TREE") && atoi(wx_getenv("WX_LATTICE_TREE")) == 0);
-    return !off && (n == 4096 || n == 2048 || n == 1024 || wx_lattice_trees_short(n, filt)) && wx_lattice_applicable_f64(filt);
+    return (n == 4096 || n == 2048 || n == 1024 || wx_lattice_trees_short(n, filt)) && wx_lattice_applicable_f64(filt);
 }
 
 int wx_lattice_tree_f64(bool inverse, const double *x, double *y, int64_t n, int L, int64_t batch, int64_t in_stride,
@@ -282,8 +266,7 @@ WX_T32(0, f) WX_T32(0, i) WX_T32(1, f) WX_T32(1, i) WX_T32(2, f) WX_T32(2, i)
 #undef WX_T32
 bool wx_lattice_tree_applicable_f32(int64_t n, const WxFilt &filt)
 {
-    static const bool off = wx_getenv("WX_LATTICE_TREE32") && atoi(wx_getenv("WX_LATTICE_TREE32")) == 0;
-    return !off && wx_lattice_tree_applicable_f64(n, filt);
+    return wx_lattice_tree_applicable_f64(n, filt);
 }
 int wx_lattice_tree_f32(bool inverse, const float *x, float *y, int64_t n, int L, int64_t batch, int64_t in_stride, const WxFilt &filt,
                         const uint8_t *dstatus, int64_t nstatus, hipStream_t st, const WxThreshArg *thr, int64_t out_stride)

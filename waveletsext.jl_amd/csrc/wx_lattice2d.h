@@ -993,17 +993,15 @@ template <int HB> static bool l2_prepare(const WxFilt &filt, int L, bool inverse
 // geometry of the fused launch for `batch` images: groups of 8 MiB (64 tasks), second pass 12 groups behind the first (1536 tickets: three
 // times the tasks in flight on 256 CUs -- the dependency of a task is looked at while the task before it computes), ring of 24 groups =
 // 192 MiB (profiles/r06_cfg4_fused.md: 2.69 ms; 8 / 16 groups 2.75 ms; less than 64 MiB behind: 3.3 ... 4.1 ms); a batch of at most 24
-// groups is its own ring (no slot is reused).  WX_L2F_G / _D / _K (knobs) override.
+// groups is its own ring (no slot is reused).
 template <int HB> static void l2_fuse_plan(int64_t batch, WxL2Fuse &fz)
 {
     typedef L2G<HB> G;
-    static const int eg = wx_getenv("WX_L2F_G") ? atoi(wx_getenv("WX_L2F_G")) : 0, ed = wx_getenv("WX_L2F_D") ? atoi(wx_getenv("WX_L2F_D")) : 0,
-                     ek = wx_getenv("WX_L2F_K") ? atoi(wx_getenv("WX_L2F_K")) : 0;
     const int64_t per = HB == 1 ? 2 : 1;
     fz.units = (int)((batch + per - 1) / per);
-    fz.G = eg > 0 ? eg : 64 / (G::R / G::BW);
-    fz.D = ed > 0 ? ed : 12;
-    fz.K = ek > fz.D ? ek : 2 * fz.D;
+    fz.G = 64 / (G::R / G::BW);
+    fz.D = 12;
+    fz.K = 2 * fz.D;
     if (fz.K > WX_L2F_MAXK) fz.K = WX_L2F_MAXK;
     if (fz.D >= fz.K) fz.D = fz.K - 1;
     fz.NG = (fz.units + fz.G - 1) / fz.G;
@@ -1080,7 +1078,6 @@ static int wx_lattice2d_fused_launch(const float *src, float *dst, float *ring, 
 template <int HB>
 static int wx_lattice2d_launch(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, bool inverse, int pass, hipStream_t st)
 {
-    static const bool blocked = WX_L2D_W == 4 && !(wx_getenv("WX_L2D_BLOCKED") && atoi(wx_getenv("WX_L2D_BLOCKED")) == 0);
     WxLat2 cf;
     WxL2M mm;
     if (!l2_prepare<HB>(filt, L, inverse, cf, mm)) return 0;
@@ -1090,8 +1087,8 @@ static int wx_lattice2d_launch(const float *src, float *dst, int64_t m, int L, i
     // Since round 6 a transform is ONE launch of k_lat2d_fused_f32; what is still built of the one-launch-per-pass form: the blocked pair
     // for the forward transform of 256 x 256 images (at full depth its fused kernel spills: the launcher above declines), and the pair of
     // db4 in every geometry and direction so that the fused launch can be timed against it on any box (WX_L2D_FUSED=0).  Anything else:
-    // 0 = not ours, the caller takes the strip kernels.  (The unblocked variant -- pass 0, WX_L2D_BLOCKED=0 -- is gone.)
-    if (!blocked || (pass != 1 && pass != 2)) return 0;
+    // 0 = not ours, the caller takes the strip kernels.  (The unblocked variant -- pass 0 -- is gone.)
+    if (WX_L2D_W != 4 || (pass != 1 && pass != 2)) return 0;
     const bool bl = pass == 2;
     const int nsq = wx_lat_stages(filt.F);
     if (!((HB == 1 && !inverse) || nsq == 4)) return 0;

@@ -4,8 +4,7 @@ bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out);
 // 0 = not applicable, 1 = launched, < 0 = error.  x: (8192, batch) dense, y likewise, L = 7 .. 13 levels
 int wx_lattice_wpt8k_f64(const double *x, double *y, int L, int64_t batch, const WxFilt &filt, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE_8K") && atoi(wx_getenv("WX_LATTICE_8K")) == 0;
-    if (off || L < 7 || L > 13 || filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || x == y) return 0;
+    if (L < 7 || L > 13 || filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || x == y) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     WxLat cf;
     if (!wx_lattice_factor(filt, L - 1, false, &cf)) return 0;

@@ -4,8 +4,7 @@ bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out);
 // xw: leaves of signal b at xw + b in_stride (dense or the last column of packet tables), y: (8192, batch)
 int wx_lattice_iwpt8k_f64(const double *xw, double *y, int L, int64_t batch, int64_t in_stride, const WxFilt &filt, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE_8K") && atoi(wx_getenv("WX_LATTICE_8K")) == 0;
-    if (off || L < 7 || L > 13 || filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || xw == y) return 0;
+    if (L < 7 || L > 13 || filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || xw == y) return 0;
     if ((reinterpret_cast<uintptr_t>(xw) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     if (in_stride < 8192 || (in_stride & 3)) return 0;
     WxLat cf;

@@ -42,10 +42,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 int wx_lattice_tree8k_fwd_f64(const double *x, double *y, int64_t batch, const WxFilt &filt, const uint8_t *dstatus0, int depth0,
                               const uint8_t *dstatus1, int depth1, hipStream_t st)
 {
-    static const bool off = (wx_getenv("WX_LATTICE_8K") && atoi(wx_getenv("WX_LATTICE_8K")) == 0) ||
-                            (wx_getenv("WX_LATTICE_8KTF") && atoi(wx_getenv("WX_LATTICE_8KTF")) == 0);
-    static const int wpe = wx_getenv("WX_LATTICE_8KTF_WPE") ? atoi(wx_getenv("WX_LATTICE_8KTF_WPE")) : 1;
-    if (off || filt.F < 2 || filt.F > 16 || (filt.F & 1) || batch <= 0 || batch > 0x7fffffff || x == y || depth0 > 12 || depth1 > 12) return 0;
+    if (filt.F < 2 || filt.F > 16 || (filt.F & 1) || batch <= 0 || batch > 0x7fffffff || x == y || depth0 > 12 || depth1 > 12) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     WxLatW cw;
     if (!wx_lattice_factor(filt, 1, false, &cw.c)) return 0;
@@ -63,10 +60,7 @@ int wx_lattice_tree8k_fwd_f64(const double *x, double *y, int64_t batch, const W
     if (rc == WX_OK) rc = wx_lat8k_child_tab(dstatus1, depth1, scr, st, &t1);
     if (rc != WX_OK) return rc;
 #define WX_GO8F(NSS)                                                                                                      \
-    case NSS:                                                                                                             \
-        if (wpe == 2) hipLaunchKernelGGL((k_lat_wpt_treesc8k_f64<NSS, 2>), dim3((unsigned)batch), dim3(128), 0, st, x, y, batch, cw, t0, t1, filt); \
-        else hipLaunchKernelGGL((k_lat_wpt_treesc8k_f64<NSS, 1>), dim3((unsigned)batch), dim3(128), 0, st, x, y, batch, cw, t0, t1, filt); \
-        break;
+    case NSS: hipLaunchKernelGGL((k_lat_wpt_treesc8k_f64<NSS, 1>), dim3((unsigned)batch), dim3(128), 0, st, x, y, batch, cw, t0, t1, filt); break;
     switch (wx_lat_stages(filt.F)) {
         WX_GO8F(1) WX_GO8F(2) WX_GO8F(3) WX_GO8F(4)
     default: return 0;

@@ -7,8 +7,7 @@ bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out);
 int wx_lattice_tree8k_inv_f64(const double *x, double *y, int64_t batch, const WxFilt &filt, const uint8_t *dstatus0, int depth0,
           const uint8_t *dstatus1, int depth1, hipStream_t st)
 {
-    static const bool off = wx_getenv("WX_LATTICE_8K") && atoi(wx_getenv("WX_LATTICE_8K")) == 0;
-    if (off || filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || x == y || depth0 > 12 || depth1 > 12) return 0;
+    if (filt.F < 2 || filt.F > 20 || batch <= 0 || batch > 0x7fffffff || x == y || depth0 > 12 || depth1 > 12) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 31) return 0;
     WxLatW cw;
     if (!wx_lattice_factor(filt, 1, true, &cw.c)) return 0;

@@ -132,9 +132,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
     auto noise = [&](double (&regs)[64]) {
         double sg[dn_nc(CB)];
         const bool act = SELC ? ((lane >> SH) & 1) != 0 : true;
-#ifdef WX_DN_NOSEL             // timing experiment of profiles/r06_denoise_onepass.md section 3: the estimate replaced by a register read (wrong results)
-        for (int q = 0; q < dn_nc(CB); ++q) sg[q] = regs[2 + q];
-#else
         // 4096 ... 512 samples at three wavefronts per SIMD: 17 of the 32 registers the estimate does not read (root bit clear) wait in the exchange
         // window, which is idle here -- left to the register allocator they went to scratch and came back (21 doubles per lane: the kernel moved
         // 1.33 x its algorithmic bytes through HBM, profiles/r06_denoise_onepass.md)
@@ -159,7 +156,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
 #pragma unroll
             for (int j = 0; j < NST; ++j) asm volatile("" : "+v"(regs[((j >> CB) << (CB + 1)) | (j & ((1 << CB) - 1))]));  // no use above the wait
         }
-#endif
 #pragma unroll
         for (int q = 0; q < dn_nc(CB); ++q) {
             // signal of the wavefront: index bits SH - 1 .. 0; one lane of its group writes

@@ -14,12 +14,8 @@ WX_G32(0) WX_G32(1) WX_G32(2) WX_G32(3) WX_G32(5) WX_G32(6)
 int wx_lattice_f32(bool inverse, const float *x, float *y, int64_t n, int L, int64_t batch, int64_t in_stride, const WxFilt &filt,
                    hipStream_t st)
 {
-    static const bool off = (wx_getenv("WX_LATTICE") && atoi(wx_getenv("WX_LATTICE")) == 0) ||
-                            (wx_getenv("WX_LATTICE_F32") && atoi(wx_getenv("WX_LATTICE_F32")) == 0);
-    if (off) return 0;
     // shorter signals: 2^SH of them per wavefront (wx_lattice_sg32.h)
-    static const bool off_g = wx_getenv("WX_LATTICE_G32") && atoi(wx_getenv("WX_LATTICE_G32")) == 0;
-    if (n != 4096 && !off_g) {
+    if (n != 4096) {
         switch (n) {
         case 2048: return wx_lattice_g32_1(inverse, x, y, n, L, batch, in_stride, filt, st);
         case 1024: return wx_lattice_g32_2(inverse, x, y, n, L, batch, in_stride, filt, st);
@@ -30,11 +26,10 @@ int wx_lattice_f32(bool inverse, const float *x, float *y, int64_t n, int L, int
         default: return 0;
         }
     }
-    if (n == 4096 && !off_g) {                               // pairs of signals in Float32 arithmetic; 0 = not taken (odd batch in place, one signal)
-        const int r = wx_lattice_g32_0(inverse, x, y, n, L, batch, in_stride, filt, st);
-        if (r) return r;
-    }
-    if (n != 4096 || L < 6 || L > 12 || filt.F < 4 || batch <= 0 || batch > 0x7fffffff) return 0;
+    // 4096 samples: pairs of signals in Float32 arithmetic; 0 = not taken (odd batch in place, one signal)
+    const int r = wx_lattice_g32_0(inverse, x, y, n, L, batch, in_stride, filt, st);
+    if (r) return r;
+    if (L < 6 || L > 12 || filt.F < 4 || batch <= 0 || batch > 0x7fffffff) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return 0;
     if (inverse && (in_stride & 3)) return 0;
     WxLat cf;

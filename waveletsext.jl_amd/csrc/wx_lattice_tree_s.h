@@ -88,12 +88,12 @@ int WX_LAT_TREES_FN(f32)(const float *x, float *y, int64_t n, int L, int64_t bat
 {
     // Float32 arithmetic on pairs of signals (lat_f2v, as wx_lattice_tree32.h does from 1024 samples up) where it measured faster: 128 and 256
     // samples, both directions (random trees 0.47-0.60 -> 0.43-0.45 ms per GiB, pyramids 0.45-0.53 -> 0.41-0.44); 64 samples (inverse 0.42 -> 0.52)
-    // and 512 samples (inverse 0.44-0.52 -> 0.56) keep Float64 registers.  Filters up to 8 taps, dense leaves.  WX_TREES32_PAIRS = 0 / 1: never / always.
-    static const int pk = wx_getenv("WX_TREES32_PAIRS") ? atoi(wx_getenv("WX_TREES32_PAIRS")) : -1;
-    const bool pairs = pk >= 0 ? pk != 0 : (WX_LAT_TREES_SH == 4 || WX_LAT_TREES_SH == 5);
-    if (pairs && col_stride == 0 && filt.F <= 8) {
-        const int r = wx_lattice_trees_launch<float, WX_LAT_TREES_SH, WX_LAT_TREES_INV, 4, true>(x, y, n, L, batch, in_stride, col_stride, filt, dstatus, nstatus, st, out_stride);
-        if (r) return r;
+    // and 512 samples (inverse 0.44-0.52 -> 0.56) keep Float64 registers.  Filters up to 8 taps, dense leaves.
+    if constexpr (WX_LAT_TREES_SH == 4 || WX_LAT_TREES_SH == 5) {
+        if (col_stride == 0 && filt.F <= 8) {
+            const int r = wx_lattice_trees_launch<float, WX_LAT_TREES_SH, WX_LAT_TREES_INV, 4, true>(x, y, n, L, batch, in_stride, col_stride, filt, dstatus, nstatus, st, out_stride);
+            if (r) return r;
+        }
     }
     return wx_lattice_trees_launch<float, WX_LAT_TREES_SH, WX_LAT_TREES_INV, 8>(x, y, n, L, batch, in_stride, col_stride, filt, dstatus, nstatus, st, out_stride);
 }

@@ -4,7 +4,7 @@
 // Reference: Wavelets.jl's wpt / iwpt with a tree::BitVector as called by wptall / iwptall (dwt/dwt_all.jl:152-166, 210-225),
 // iwpd by tree (DWT.jl:340-351: getbasiscoef, Utils.jl:101-134, then iwpt), denoise(:wpt) (Denoising.jl:527).
 //
-// The first form (k_lat_wpt_tree_f64 in wx_lattice_dev.h) lets the leaves of depth l < 6 leave through their own exchange
+// The first form (round 3, no longer built) let the leaves of depth l < 6 leave through their own exchange
 // right after level l: up to five dependent exchange chains per signal, which is what holds random trees at 0.42 / 0.36 of
 // the HBM peak.  Here a leaf simply stops changing: the in-place lattice keeps coefficient (path p of d levels, position k
 // in the node) at index i = k << d | p (bit t of p = branch of level t + 1), so

@@ -34,16 +34,9 @@ static int wx_force_generic_swt() { return wx_force_generic(); }
 enum { WX_LAYOUT_DWT = 0, WX_LAYOUT_WPT = 1, WX_LAYOUT_WPD = 2 };
 
 // smallest dilation at which the fused sdwt / isdwt kernels slide register windows over a residue class (below it: one
-// LDS read per tap)
-static int wx_sdwt_window_min()
-{
-    static int v = -1;
-    if (v < 0) { const char *e = wx_getenv("WX_SDWT_WIN_S"); v = (e && atoi(e) >= 1) ? atoi(e) : 0; }
-    return v;
-}
-// default: every level for filters of four taps or more (db4, n = 4096, L = 6: sdwt 1.48 -> 1.02 ms, isdwt 2.40 -> 1.85 ms --
+// LDS read per tap): every level for filters of four taps or more (db4, n = 4096, L = 6: sdwt 1.48 -> 1.02 ms, isdwt 2.40 -> 1.85 ms --
 // the 4-way LDS bank conflicts of the narrow classes cost less than the tap-by-tap loop); Haar has nothing to slide over
-static int wx_sdwt_window_min_for(int F) { const int e = wx_sdwt_window_min(); return e ? e : (F >= 4 ? 1 : 16); }
+static int wx_sdwt_window_min_for(int F) { return F >= 4 ? 1 : 16; }
 
 static __device__ __forceinline__ void wx_fwd_cols(int layout, int L, int d, int b, int &pcol, int &lcol, int &hcol)
 {
@@ -317,8 +310,7 @@ __global__ __launch_bounds__(256) void k_acwpd_top_combine(const double *__restr
 // moments of ALL its columns; 1 = done, 0 = not applicable (the caller takes the three plain passes + the moment kernel), < 0 = error
 bool wx_acwpd_top_moments_ok(int64_t n, int D0)
 {
-    static const bool off = wx_getenv("WX_ACWPD_TOPMOM") && atoi(wx_getenv("WX_ACWPD_TOPMOM")) == 0;
-    if (off || wx_force_generic_swt() || D0 < 2 || (D0 & 1) || D0 > 14) return false;
+    if (wx_force_generic_swt() || D0 < 2 || (D0 & 1) || D0 > 14) return false;
     return n == 1024 || n == 2048 || n == 4096;
 }
 int wx_dev_acwpd_top_moments(const double *x, double *tab, int64_t n, int D0, int64_t batch, const WxAcFilt &ac, double *sum, double *sumsq,
@@ -1233,12 +1225,7 @@ __global__ __launch_bounds__(256) void k_iacwpd(const T *__restrict__ xw, T *__r
 // ------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------
-static int64_t wx_swtfwd_lds_bytes()
-{
-    static int64_t v = -1;
-    if (v < 0) { const char *e = wx_getenv("WX_SWTFWD_LDS_KIB"); v = (e && atoi(e) > 0 && atoi(e) <= 64 ? atoi(e) : 32) * 1024; }
-    return v;
-}
+static int64_t wx_swtfwd_lds_bytes() { return 32 * 1024; }
 static int wx_grid1(int64_t total)
 {
     int64_t g = (total + 255) / 256;
@@ -1340,8 +1327,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
     }
-    if (layout == WX_LAYOUT_DWT && L >= 2 && n == 1024 * (int64_t)(128 / sizeof(T)) && !wx_force_generic_swt() &&
-        !(wx_getenv("WX_SDWT_INPLACE") && atoi(wx_getenv("WX_SDWT_INPLACE")) == 0)) {
+    if (layout == WX_LAYOUT_DWT && L >= 2 && n == 1024 * (int64_t)(128 / sizeof(T)) && !wx_force_generic_swt()) {
         // the column fills more than half of a CU's LDS: in-place fused kernel, one workgroup of 1024 threads per CU
         constexpr int NPT = 128 / sizeof(T);
         typedef void (*KFI)(const T *, T *, int, int64_t, int, WxFilt, WxAcFilt);
@@ -1363,9 +1349,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
     // stream-ordered scratch buffer
     // with the sliding windows of k_swt_fwd_multi_rc the two-level passes win for every filter length of the library
     // (coif6 / db10, n = 16384, L = 12: 20.3 -> 13.4 ms against single levels)
-    static const int kf_maxf = wx_getenv("WX_SWTFWD_KF_MAXF") ? atoi(wx_getenv("WX_SWTFWD_KF_MAXF")) : 20;
-    static const int k3_maxf = wx_getenv("WX_SWTFWD_K3_MAXF") ? atoi(wx_getenv("WX_SWTFWD_K3_MAXF")) : 4;
-    const int KF = (!ac && layout == WX_LAYOUT_WPT && !wx_force_generic_swt()) ? (filt.F <= k3_maxf ? 3 : (filt.F <= kf_maxf ? 2 : 1)) : 1;
+    const int KF = (!ac && layout == WX_LAYOUT_WPT && !wx_force_generic_swt()) ? (filt.F <= 4 ? 3 : (filt.F <= 20 ? 2 : 1)) : 1;
     double *dcoef = nullptr;
     int *dshift = nullptr;
     int d = 0;
@@ -1379,9 +1363,8 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         const int K = (KF > 1 && dstop - d >= 2) ? (dstop - d >= KF ? KF : dstop - d) : 1;
         int64_t gy = batch;
         if (gy > 65535) gy = 65535;
-        // swpd / acwpd: two levels per pass while three columns fit the LDS (WX_SWPD_TWO=0: one level per pass)
-        static const bool two_off = wx_getenv("WX_SWPD_TWO") && atoi(wx_getenv("WX_SWPD_TWO")) == 0;
-        if (K == 1 && layout == WX_LAYOUT_WPD && dstop - d >= 2 && 3 * lds <= 160 * 1024 && !two_off && !wx_force_generic_swt()) {
+        // swpd / acwpd: two levels per pass while three columns fit the LDS
+        if (K == 1 && layout == WX_LAYOUT_WPD && dstop - d >= 2 && 3 * lds <= 160 * 1024 && !wx_force_generic_swt()) {
             auto k2 = ac ? k_swpd_fwd_two<T, true> : k_swpd_fwd_two<T, false>;
             if (3 * lds > 64 * 1024)
                 WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -1495,18 +1478,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
     return WX_OK;
 }
 
-static int64_t wx_swtinv_lds_bytes()
-{
-    static int64_t v = -1;
-    if (v < 0) { const char *e = wx_getenv("WX_SWTINV_LDS_KIB"); v = (e && atoi(e) > 0 && atoi(e) <= 64 ? atoi(e) : 32) * 1024; }
-    return v;
-}
-static int wx_swtinv_threads()
-{
-    static int v = -1;
-    if (v < 0) { const char *e = wx_getenv("WX_SWTINV_NT"); v = (e && (atoi(e) == 64 || atoi(e) == 128 || atoi(e) == 256)) ? atoi(e) : 512; }
-    return v;
-}
+static int64_t wx_swtinv_lds_bytes() { return 32 * 1024; }
 // inverse schedule (see WxSwtInvPlan): fused two-level (three for F <= 4) passes for the average-based full iswpt while the
 // 2^K descendant tiles of >= 64-byte runs fit in 128 KiB of LDS, single levels otherwise
 void wx_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, size_t esz, bool has_tree, WxSwtInvPlan *P,
@@ -1594,8 +1566,7 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
     }
-    if (layout == WX_LAYOUT_DWT && sm < 0 && L >= 2 && n == 1024 * (int64_t)(128 / sizeof(T)) &&
-        !wx_force_generic_swt() && !(wx_getenv("WX_SDWT_INPLACE") && atoi(wx_getenv("WX_SDWT_INPLACE")) == 0)) {
+    if (layout == WX_LAYOUT_DWT && sm < 0 && L >= 2 && n == 1024 * (int64_t)(128 / sizeof(T)) && !wx_force_generic_swt()) {
         // the three columns of k_isdwt_avg_fused do not fit: reconstruction in place in one column of LDS, details from global
         constexpr int NPT = 128 / sizeof(T);
         auto ki = k_isdwt_avg_fused_ip<T, NPT>;
@@ -1714,10 +1685,9 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
             const int64_t total = batch * nodes_d * per_node;
             // average based, long columns: out of an LDS tile (k_swt_inv_level_tile) while the halo s (F - 1) of the dilated taps stays small
             // against the tile -- the top levels, which is where the per-sample kernel is slow
-            static const bool tile_off = wx_getenv("WX_SWTINV_TILE") && atoi(wx_getenv("WX_SWTINV_TILE")) == 0;
             const int64_t halo = ((int64_t)1 << d) * (filt.F - 1);
             const int Ptile = 2048;
-            if (!tile_off && sm_mode == 0 && n >= 2 * Ptile && n % Ptile == 0 && halo <= 512 && !wx_force_generic_swt()) {
+            if (sm_mode == 0 && n >= 2 * Ptile && n % Ptile == 0 && halo <= 512 && !wx_force_generic_swt()) {
                 const size_t ldst = (size_t)2 * (Ptile + 2 * halo) * sizeof(T);
                 const int64_t units = batch * nodes_d * (n / Ptile);
                 const int64_t gt = units < 256 * 8 ? units : 256 * 8;

@@ -1,12 +1,10 @@
 // wx_toptile.hip -- tree bookkeeping and launcher of the multi-level top pass (wx_toptile.h); forward kernels are instantiated here,
 // inverse kernels in wx_toptile_i.hip.
 #include "wx_toptile.h"
-#include <cstdlib>
 
 bool wx_top_levels_ok(int F)
 {
-    static const bool off = wx_getenv("WX_TOPTILE") && atoi(wx_getenv("WX_TOPTILE")) == 0;
-    return !off && F >= 2 && F <= 20 && (F & 1) == 0;
+    return F >= 2 && F <= 20 && (F & 1) == 0;
 }
 
 bool wx_top_tree(int NL, unsigned split, unsigned deep, const int *W2, WxTopTree *P, bool wpd)
@@ -50,11 +48,9 @@ int64_t wx_top_grid(int64_t ntiles, size_t lds)
         if (cus <= 0) cus = 256;
         cus_of[dev & 63].store(cus, std::memory_order_relaxed);
     }
-    static const int env = wx_getenv("WX_TOPTILE_WGS") ? atoi(wx_getenv("WX_TOPTILE_WGS")) : 0;
     int per = (int)((160 * 1024) / (lds + 512));
     if (per < 1) per = 1;
     if (per > 8) per = 8;
-    if (env > 0) per = env;
     const int64_t g = (int64_t)cus * per;
     return ntiles < g ? ntiles : g;
 }
