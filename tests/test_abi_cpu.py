@@ -159,6 +159,65 @@ def test_redundant_argument_errors(wx):
     np.testing.assert_allclose(q, [-0.35355339, 0.70710678, -0.35355339], atol=1e-8)
 
 
+def test_redundant2d_argument_errors(wx):
+    """the 2-D redundant entry points refuse bad arguments with the reference's error classes before any device is
+    touched (so this runs without one): through the Python layer, and at the C ABI itself"""
+    import ctypes
+    wt = wx.wavelet(wx.WT.db4)
+    img = np.zeros((8, 16))
+    for fwd in (wx.sdwt, wx.swpt, wx.swpd, wx.acdwt, wx.acwpt, wx.acwpd):
+        with pytest.raises(wx.ArgumentError):
+            fwd(img, wt, 0)                                                     # L >= 1
+        with pytest.raises(wx.ArgumentError):
+            fwd(img, wt, 4)                                                     # SWT.jl:137-139, ACWT.jl:135-137: 8 rows
+    L = 2
+    for sm in (0, 1 << L):
+        with pytest.raises(AssertionError):
+            wx.isdwt(np.zeros((8, 16, 3 * L + 1)), wt, sm)                      # SWT.jl:293, Utils.jl:298
+    with pytest.raises(AssertionError):
+        wx.iswpt(np.zeros((8, 16, 16)), wt, 1 << L)                             # main2depthshift: sm < 1 << L
+    with pytest.raises(AssertionError):
+        wx.iswpt(np.zeros((8, 16, 256)), wt)                                    # SWT.jl:656: 4 levels of 8 rows
+    for inv in (wx.iswpt, wx.iacwpt):
+        with pytest.raises(wx.ArgumentError):
+            inv(np.zeros((8, 16, 8)), wt)                                       # SWT.jl:653, ACWT.jl:617: not a power of 4
+    bad = np.zeros(21, dtype=bool)
+    bad[1] = True                                                               # a child without its parent
+    for inv in (wx.iswpd, wx.iacwpd):
+        with pytest.raises(AssertionError):
+            inv(np.zeros((8, 16, 21)), wt, bad)                                 # SWT.jl:1101, ACWT.jl:973
+        with pytest.raises(AssertionError):
+            inv(np.zeros((8, 16, 21)), wt, np.ones(5, dtype=bool))              # wrong tree length
+        with pytest.raises(IndexError):
+            inv(np.zeros((8, 16, 5)), wt, wx.maketree(8, 16, 2, "full"))        # the tree reaches below the last slice
+    with pytest.raises(AssertionError):
+        wx.iswpd(np.zeros((8, 16, 21)), wt, None, 4)                            # sm < 1 << (depth of the table)
+    # the C ABI makes the same checks itself (status codes of include/waveletsext_hip.h), whatever the binding does
+    lib = ctypes.CDLL(wx.LIB_PATH)
+    q = np.ascontiguousarray(wt.qmf, dtype=np.float64)
+    qp, F = q.ctypes.data_as(ctypes.c_void_p), ctypes.c_int(q.size)
+    buf = np.zeros(8 * 16 * 21)
+    p = buf.ctypes.data_as(ctypes.c_void_p)
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    EASSERT, EARG, EBOUNDS = -1, -2, -3
+    for name in ("wx_sdwt2d_f64", "wx_swpt2d_f64", "wx_swpd2d_f64", "wx_acdwt2d_f64", "wx_acwpt2d_f64", "wx_acwpd2d_f64"):
+        assert getattr(lib, name)(p, p, i64(8), i64(16), ci(0), i64(1), qp, F, None) == EARG, name
+        assert getattr(lib, name)(p, p, i64(8), i64(16), ci(4), i64(1), qp, F, None) == EARG, name
+    for sm in (0, 4):
+        assert lib.wx_isdwt2d_f64(p, p, i64(8), i64(16), ci(2), i64(sm), i64(1), qp, F, None) == EASSERT
+    assert lib.wx_iswpt2d_f64(p, p, i64(8), i64(16), ci(2), i64(4), i64(1), qp, F, None) == EASSERT
+    assert lib.wx_iswpt2d_f64(p, p, i64(8), i64(16), ci(4), i64(-1), i64(1), qp, F, None) == EASSERT
+    t8 = np.ascontiguousarray(bad, dtype=np.uint8)
+    tp = t8.ctypes.data_as(ctypes.c_void_p)
+    assert lib.wx_iswpd2d_f64(p, p, i64(8), i64(16), i64(21), ci(0), tp, i64(21), i64(-1), i64(1), qp, F, None) == EASSERT
+    assert lib.wx_iacwpd2d_f64(p, p, i64(8), i64(16), i64(21), ci(0), tp, i64(21), i64(1), None) == EASSERT
+    full2 = np.zeros(21, dtype=np.uint8)
+    full2[:5] = 1
+    fp = full2.ctypes.data_as(ctypes.c_void_p)
+    assert lib.wx_iswpd2d_f64(p, p, i64(8), i64(16), i64(5), ci(0), fp, i64(21), i64(-1), i64(1), qp, F, None) == EBOUNDS
+    assert lib.wx_iacwpd2d_f64(p, p, i64(8), i64(16), i64(5), ci(0), fp, i64(21), i64(1), None) == EBOUNDS
+
+
 def test_header_compiles_as_c_and_example_links(tmp_path, wx):
     """include/waveletsext_hip.h is a C header: examples/roundtrip.c builds with gcc -std=c99 against the .so
     (and, without a GPU, fails loudly with the library's status instead of computing on the CPU)"""

@@ -46,6 +46,8 @@ def _declare(L):
     L.wx_build_info.restype = ctypes.c_char_p
     L.wx_debug_set_dispatch.argtypes = [_I]           # csrc/wx_debug.h: test-suite hook, not in the public header
     L.wx_debug_set_dispatch.restype = None
+    L.wx_debug_red2d_route.argtypes = [_I, _L, _L, _I, _I, _I, _I, _I]
+    L.wx_debug_red2d_route.restype = _I
     sigs = {
         # name: argtypes (without the _f64/_f32 suffix)
         "wx_wpd1d": [_P, _P, _L, _I, _L, _P, _I, _P],
@@ -216,3 +218,16 @@ def set_host_hugepages(on):
 
 def set_force_generic(on):
     lib().wx_debug_set_dispatch(2 if on == 2 else (1 if on else 0))
+
+
+RED2D_ROUTES = {1: "F1", 2: "F2", 3: "F3", 4: "I1", 5: "I2", 6: "I3", 7: "I4"}
+
+
+def red2d_route(inverse, m, n, L, elem_size, F, ac=False, shift=False):
+    """(route, R) that the 2-D redundant transforms take under the current dispatch mode (csrc/wx_debug.h:
+    wx_debug_red2d_route): forward, the route of a whole call of L levels; inverse, the route of the level of depth L - 1.
+    R is the strip height of that level for F1 / F2 / I1 and 0 otherwise."""
+    code = lib().wx_debug_red2d_route(int(bool(inverse)), m, n, L, elem_size, F, int(bool(ac)), int(bool(shift)))
+    if code < 0:
+        raise ValueError("wx_debug_red2d_route: arguments outside the transforms' domain")
+    return RED2D_ROUTES[code & 255], code >> 8

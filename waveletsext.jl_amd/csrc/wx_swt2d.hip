@@ -15,7 +15,10 @@
 // the parent with child 1.
 #include "wx_common.h"
 #include "wx_kernels.h"
+#include "wx_debug.h"
 #include <cstdlib>
+
+int wx_force_generic();   // test hook (wx_debug_set_dispatch(1), wx_debug.h): two passes instead of the one-pass levels
 
 enum { WX2_DWT = 0, WX2_WPT = 1, WX2_WPD = 2 };
 
@@ -431,6 +434,52 @@ template <typename T> static WxRedTile wx_red2d_fused_geom(int64_t m, int64_t n,
     return g;
 }
 
+// The launch routes (numbered as wx_debug.h documents them).  These two functions are the only place where a route is
+// chosen: wx_dev_red2d_fwd / wx_dev_red2d_inv launch what they return and wx_debug_red2d_route reports it.
+enum { WX_R2_F1 = 1, WX_R2_F2 = 2, WX_R2_F3 = 3, WX_R2_I1 = 4, WX_R2_I2 = 5, WX_R2_I3 = 6, WX_R2_I4 = 7 };
+
+// forward, one route per call: one pass only if every level 0..L-1 has a strip geometry; *deep: geometry of level L-1
+template <typename T> static int wx_red2d_fwd_route(int64_t m, int64_t n, int L, int F, bool ac, WxRedTile *deep)
+{
+    WxRedTile t = {0, 0, 0, 0};
+    if (L < 1 || wx_force_generic()) return WX_R2_F3;
+    for (int d = 0; d < L; ++d) {
+        t = wx_red2d_fused_geom<T>(m, n, 1 << d, F, ac);
+        if (!t.R) return WX_R2_F3;
+    }
+    *deep = t;
+    return t.CT == (int)n ? WX_R2_F1 : WX_R2_F2;
+}
+
+// inverse, one route per level d; *tile: the strip geometry of WX_R2_I1
+template <typename T> static int wx_red2d_inv_route(int64_t m, int64_t n, int d, int F, bool ac, bool shift, WxRedTile *tile)
+{
+    if (ac) return WX_R2_I4;
+    if (shift) return WX_R2_I3;
+    if (!wx_force_generic() && (m & (m - 1)) == 0 && (n & (n - 1)) == 0) {
+        const WxRedTile t = wx_red2d_fused_geom<T>(m, n, 1 << d, F, false);
+        // whole-row strips; measured against the two passes (256 images, L = 3 iswpt): 128 x 128 Float64
+        // 9.4 ms vs 12.3, 256 x 256 Float32 8.6 vs 9.8, but 256 x 256 Float64 (strips of 8 rows) 12.7 vs 11.3
+        if (t.R && t.CT == (int)n && (size_t)n * sizeof(T) <= 1024) { *tile = t; return WX_R2_I1; }
+    }
+    return WX_R2_I2;
+}
+
+template <typename T> static int wx_red2d_route_code(int inverse, int64_t m, int64_t n, int L, int F, int ac, int shift)
+{
+    WxRedTile t = {0, 0, 0, 0};
+    const int r = inverse ? wx_red2d_inv_route<T>(m, n, L - 1, F, ac != 0, shift != 0, &t)
+                          : wx_red2d_fwd_route<T>(m, n, L, F, ac != 0, &t);
+    return r + 256 * ((r == WX_R2_F1 || r == WX_R2_F2 || r == WX_R2_I1) ? t.R : 0);
+}
+
+extern "C" int wx_debug_red2d_route(int inverse, int64_t m, int64_t n, int L, int elem_size, int F, int ac, int shift)
+{
+    if (m < 1 || n < 1 || L < 1 || L > 30 || F < 2 || (elem_size != 4 && elem_size != 8)) return -1;
+    return elem_size == 8 ? wx_red2d_route_code<double>(inverse, m, n, L, F, ac, shift)
+                          : wx_red2d_route_code<float>(inverse, m, n, L, F, ac, shift);
+}
+
 // grid.x over the elements of one job, grid.y over the jobs
 static dim3 wx_grid2r(int64_t per, int64_t njobs)
 {
@@ -505,9 +554,8 @@ int wx_dev_red2d_fwd(const T *x, T *xw, int64_t m, int64_t n, int L, int layout,
     if (batch == 0 || m * n == 0) return WX_OK;
     WxAcFilt acz;
     if (ac) acz = *ac; else { acz.F = 0; acz.c1 = 0; }
-    bool all_fused = L > 0;
-    for (int d = 0; d < L; ++d) all_fused = all_fused && wx_red2d_fused_geom<T>(m, n, 1 << d, filt.F, ac != nullptr).R > 0;
-    if (all_fused) {
+    WxRedTile deep;
+    if (wx_red2d_fwd_route<T>(m, n, L, filt.F, ac != nullptr, &deep) != WX_R2_F3) {
         // scratch images of the nodes that are decomposed again: depth d in buf[d & 1] (each half of tmp holds the
         // 4^(L-1) nodes of the deepest intermediate depth)
         const int64_t half = (layout == WX2_DWT ? 1 : ((int64_t)1 << (2 * (L > 1 ? L - 1 : 0)))) * batch * m * n;
@@ -572,23 +620,18 @@ int wx_dev_red2d_inv(const T *xw, T *x, int64_t m, int64_t n, int L, int layout,
         D.cur = bufs[(d + 1) & 1]; D.cur_cols = nodes_c;
         if (d == 0) { D.out = x; D.out_cols = 1; } else { D.out = bufs[d & 1]; D.out_cols = nodes_d; }
         const int64_t jobs = batch * nodes_d;
-        if (ac) {
+        WxRedTile t = {0, 0, 0, 0};
+        const int route = wx_red2d_inv_route<T>(m, n, d, filt.F, ac, sm >= 0, &t);
+        if (route == WX_R2_I4) {
             hipLaunchKernelGGL(k_red2d_iac<T>, wx_grid2r(mn, jobs), dim3(256), 0, st, D, nodes_d);
+        } else if (route == WX_R2_I1) {
+            int64_t g = jobs * (m / t.R);
+            if (g > 256 * 8) g = 256 * 8;
+            hipLaunchKernelGGL(k_red2d_inv_fused<T>, dim3((unsigned)g), dim3(256), (size_t)2 * n * t.R * sizeof(T), st, D,
+                               nodes_d, t.R, filt);
         } else {
-            const int sm_mode = sm >= 0 ? 1 : 0;
-            const int sv = sm >= 0 ? (int)sd[d] : 0, sw = sm >= 0 ? (int)sd[d + 1] : 0;
-            if (!sm_mode && (m & (m - 1)) == 0 && (n & (n - 1)) == 0) {
-                const WxRedTile t = wx_red2d_fused_geom<T>(m, n, 1 << d, filt.F, false);
-                // whole-row strips; measured against the two passes (256 images, L = 3 iswpt): 128 x 128 Float64
-                // 9.4 ms vs 12.3, 256 x 256 Float32 8.6 vs 9.8, but 256 x 256 Float64 (strips of 8 rows) 12.7 vs 11.3
-                if (t.R && t.CT == (int)n && (size_t)n * sizeof(T) <= 1024) {
-                    int64_t g = jobs * (m / t.R);
-                    if (g > 256 * 8) g = 256 * 8;
-                    hipLaunchKernelGGL(k_red2d_inv_fused<T>, dim3((unsigned)g), dim3(256), (size_t)2 * n * t.R * sizeof(T), st, D,
-                                       nodes_d, t.R, filt);
-                    continue;
-                }
-            }
+            const int sm_mode = route == WX_R2_I3 ? 1 : 0;
+            const int sv = sm_mode ? (int)sd[d] : 0, sw = sm_mode ? (int)sd[d + 1] : 0;
             const int64_t per2 = sm_mode ? (m >> (d + 1)) * (n >> d) : mn;
             const int64_t per1 = sm_mode ? (m >> d) * (n >> d) : mn;
             hipLaunchKernelGGL(k_red2d_inv_dim2<T>, wx_grid2r(per2, jobs * 2), dim3(256), 0, st, D, tmp, nodes_d, sm_mode, sv, sw, filt);
