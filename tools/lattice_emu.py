@@ -82,6 +82,46 @@ def level(x, K, H, t, inv):
                 delay()
 
 
+def fold_matrix(t, NF, inv):
+    """csrc/wx_lattice_fold.h: the deepest log2(NF) levels of a full-depth transform (layout C, K = 5, 4, 3: nodes of 1, 2, 4 pairs)
+    as ONE NF x NF matrix on the registers {s + (64 / NF) j} of a lane -- on a node of M pairs the advances of the odd channel wrap
+    every M steps, so the composite is a fixed matrix, the same for every s and lane.  Built like the host does
+    (wx_lattice_fold_matrix): the recurrence of level() on unit vectors, in long double, rounded once.  Row-major (NF, NF)."""
+    G = 64 // NF
+    Ks = [K for K in (5, 4, 3) if (32 >> K) * 2 <= NF]                # K = 5: pairs (s, s + 32) ... K = 3: needs 8 registers
+    if not inv:
+        Ks = Ks[::-1]
+    tl = (np.asarray(t[0], dtype=np.longdouble), np.asarray(t[1], dtype=np.longdouble))
+    M = np.zeros((NF, NF), dtype=np.longdouble)
+    for j in range(NF):
+        x = np.zeros((64, 1), dtype=np.longdouble)
+        x[G * j] = 1
+        for K in Ks:
+            level(x, K, 0, tl, inv)
+        M[:, j] = x[::G, 0]
+    if not np.isfinite(M).all() or np.abs(M).max() > 1e30:
+        return None                                                   # declined: the caller keeps the lattice levels
+    return M.astype(np.float64)
+
+
+def fold_apply(x, M):
+    """lat_fold_nodes: new x[s + G i] = sum_j M[i, j] x[s + G j], every s < G and every lane"""
+    NF = len(M)
+    G = 64 // NF
+    for s in range(G):
+        x[s::G] = M @ x[s::G]
+
+
+def fold_levels(t, L, fold, inv):
+    """(matrix or None, number of deepest C levels it replaces): the fold runs at full depth for filters of 6 and more rotations"""
+    ns = len(t[0])
+    built = ns if ns <= 2 else (ns + 1) & ~1                          # wx_lat_stages_of: 5 rotations (db5) run on the kernel built for 6
+    if not fold or L != 12 or built < 6:
+        return None, 0
+    M = fold_matrix(t, fold, inv)
+    return (None, 0) if M is None else (M, int(np.log2(fold)))
+
+
 def lat_pi(L, r):
     e = 0
     for k in range(12 - L):
@@ -167,7 +207,8 @@ def wpt_emu(xsig, t, gain1, L):
     return y
 
 
-def iwpt_emu(w, t, gain1, L):
+def iwpt_emu(w, t, gain1, L, fold=0):
+    """fold = 2, 4, 8: k_lat_iwpt12_f64<NS, 2, fold> (levels 12 .. 13 - log2(fold) as one matrix per node) where it applies"""
     lane = LANES
     lds = np.full(1104, np.nan)
     pcl = np.array([bin(v).count("1") for v in lane])
@@ -187,7 +228,10 @@ def iwpt_emu(w, t, gain1, L):
         for e4 in range(16):
             rr = lat_pi_inv(L, 16 * k + e4)
             c[rr] = lds[ra + e4] * (base * (gain1 ** 2.0) ** bin(rr & mask).count("1"))
-    for K in range(5, -1, -1):
+    M, nfold = fold_levels(t, L, fold, True)
+    if M is not None:
+        fold_apply(c, M)
+    for K in range(5 - nfold, -1, -1):
         if L > 6 + K:
             level(c, K, 0, t, True)
     bb = np.empty((64, 64))

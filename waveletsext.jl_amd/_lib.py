@@ -217,7 +217,20 @@ def set_host_hugepages(on):
 
 
 def set_force_generic(on):
-    lib().wx_debug_set_dispatch(2 if on == 2 else (1 if on else 0))
+    lib().wx_debug_set_dispatch(on if on in (2, 3) else (1 if on else 0))
+
+
+def lattice_fold_matrix(qmf, nf, inverse=True):
+    """csrc/wx_debug.h: the (nf, nf) node matrix that folds the deepest log2(nf) levels of the full-depth lattice transform, or
+    None when this filter does not fold"""
+    import numpy as np
+    q = np.ascontiguousarray(qmf, dtype=np.float64)
+    m = np.zeros((nf, nf), dtype=np.float64)
+    f = lib().wx_debug_lattice_fold
+    f.argtypes = [_P, _I, _I, _I, _P]
+    f.restype = _I
+    got = f(q.ctypes.data, int(q.size), int(nf), 1 if inverse else 0, m.ctypes.data)
+    return m if got == nf else None
 
 
 RED2D_ROUTES = {1: "F1", 2: "F2", 3: "F3", 4: "I1", 5: "I2", 6: "I3", 7: "I4"}

@@ -13,6 +13,7 @@ const char *wx_err_cstr();
 static std::atomic<int> g_force_generic{0};
 int wx_force_generic() { return g_force_generic.load() == 1; }
 int wx_skip_register_kernels() { return g_force_generic.load() == 2; }
+int wx_lattice_no_fold() { return g_force_generic.load() == 3; }          // wx_lattice_fold.h
 
 extern "C" {
 
@@ -24,7 +25,7 @@ int wx_device_count(void)
     if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return 0; }
     return n;
 }
-void wx_debug_set_dispatch(int on) { g_force_generic.store(on == 2 ? 2 : (on ? 1 : 0)); }   // wx_debug.h, not the public ABI
+void wx_debug_set_dispatch(int on) { g_force_generic.store((on == 2 || on == 3) ? on : (on ? 1 : 0)); }   // wx_debug.h, not the public ABI
 
 }  // extern "C"
 

@@ -6,8 +6,13 @@
 extern "C" {
 #endif
 /* 0 = normal dispatch; 1 = one level per launch instead of the fused kernels; 2 = keep the fused LDS kernels but skip the
- * register-resident ones (Haar Walsh-Hadamard, lattice) */
+ * register-resident ones (Haar Walsh-Hadamard, lattice); 3 = normal dispatch, but the full-depth lattice inverse without the fold
+ * of its deepest levels (wx_lattice_fold.h): the general kernel, as for every other depth */
 void wx_debug_set_dispatch(int mode);
+
+/* The node matrix (row-major, NF x NF, NF = 2, 4 or 8) that folds the deepest log2(NF) levels of a full-depth lattice transform for
+ * the QMF q of length F, as the launchers build it (wx_lattice_fold_matrix).  Returns NF, or 0 when this filter does not fold. */
+int wx_debug_lattice_fold(const double *q, int F, int NF, int inverse, double *m);
 
 /* Which kernels the 2-D redundant transforms (wx_swt2d.hip) launch under the current dispatch mode; computed by the very
  * function the launch code calls.  elem_size 8 / 4 = Float64 / Float32, F = filter length, ac = autocorrelation family,

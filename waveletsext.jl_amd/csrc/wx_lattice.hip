@@ -1,7 +1,7 @@
 // wx_lattice.hip -- host side of the lattice kernels (device code: wx_lattice_dev.h): factorisation, launchers for
 // 4096-sample signals; the interleaved shorter signals are launched from wx_lattice_sh.hip (a separate translation unit so
 // that the two sets of kernel instantiations compile in parallel)
-#include "wx_lattice_dev.h"
+#include "wx_lattice_fold.h"
 
 // Lattice factorisation of the polyphase matrix (long double): G(w) = [[Qe, Qo], [-w^J Qo(1/w), w^J Qe(1/w)]]
 // = R_J Lambda(w) R_{J-1} ... Lambda(w) R_0 with R_j = c_j [[1, t_j], [-t_j, 1]], Lambda = diag(1, w).
@@ -93,6 +93,65 @@ bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out)
     return std::isfinite(out->g0) && fabsl(gL) > 1e-60L && fabsl(gL) < 1e60L;
 }
 
+// Node matrix of the deepest log2(NF) levels of a full-depth transform (wx_lattice_fold.h): the shear and advance recurrence of
+// lat_level<K, 0, NS, INV> for K = 5, 4, 3 (inverse; 3, 4, 5 forward) on the unit vectors of one register group {s + (64 / NF) j}, in
+// long double from the rounded p[j], kap[j] the device uses, rounded once.  Level K is bit b = K - 6 + log2(NF) of the group index:
+// 2^b sequences of NF >> (b + 1) pairs.  The form the device applies is the dense matrix itself, so there is no factorisation whose
+// error could be checked; declined (false: the caller launches the general kernel) when an entry is not finite or exceeds 1e30 --
+// the lattice keeps its intermediates within 1e+-60 (wx_lattice_factor), a larger entry could carry a product out of range.
+bool wx_lattice_fold_matrix(const WxLat &cf, int NS, int NF, bool inverse, double *m)
+{
+    if (NS < 1 || NS > WX_LAT_MAXS || (NF != 2 && NF != 4 && NF != 8)) return false;
+    const int nb = NF == 2 ? 1 : (NF == 4 ? 2 : 3);
+    for (int col = 0; col < NF; ++col) {
+        long double x[8] = {};
+        x[col] = 1;
+        for (int k = 0; k < nb; ++k) {
+            const int b = inverse ? nb - 1 - k : k, S = 1 << b, M = NF >> (b + 1);
+            for (int s = 0; s < S; ++s) {
+                long double u[4], w[4], old[4];
+                for (int mm = 0; mm < M; ++mm) { u[mm] = x[s + ((2 * mm) << b)]; w[mm] = x[s + ((2 * mm) << b) + S]; }
+                auto shift = [&](int sh) {                           // pair mm takes the odd value of pair mm + sh, cyclically
+                    for (int mm = 0; mm < M; ++mm) old[mm] = w[mm];
+                    for (int mm = 0; mm < M; ++mm) w[mm] = old[(((mm + sh) % M) + M) % M];
+                };
+                if (!inverse) {
+                    for (int j = 0; j < NS; ++j) {
+                        for (int mm = 0; mm < M; ++mm) { u[mm] += (long double)cf.p[j] * w[mm]; w[mm] -= (long double)cf.kap[j] * u[mm]; }
+                        if (j + 1 < NS) shift(1);
+                    }
+                    shift(-(NS - 1));
+                } else {
+                    shift(NS - 1);
+                    for (int j = NS - 1; j >= 0; --j) {
+                        for (int mm = 0; mm < M; ++mm) { w[mm] += (long double)cf.kap[j] * u[mm]; u[mm] -= (long double)cf.p[j] * w[mm]; }
+                        if (j > 0) shift(-1);
+                    }
+                }
+                for (int mm = 0; mm < M; ++mm) { x[s + ((2 * mm) << b)] = u[mm]; x[s + ((2 * mm) << b) + S] = w[mm]; }
+            }
+        }
+        for (int i = 0; i < NF; ++i) {
+            if (!std::isfinite((double)x[i]) || fabsl(x[i]) > 1e30L) return false;
+            m[NF * i + col] = (double)x[i];
+        }
+    }
+    return true;
+}
+
+// test hook (wx_debug.h): the node matrix the launchers would use for this filter; 0 = no fold (fewer than 6 rotations, no lattice, declined)
+extern "C" int wx_debug_lattice_fold(const double *q, int F, int NF, int inverse, double *m)
+{
+    if (!q || !m || F < 2 || F > WX_MAXF) return 0;
+    WxFilt filt = {};
+    for (int i = 0; i < F; ++i) filt.q[i] = q[i];
+    filt.F = F;
+    WxLat cf;
+    const int NS = wx_lat_stages(F);
+    if (NS < 6 || NS > WX_LAT_MAXS || !wx_lattice_factor(filt, 12, inverse != 0, &cf)) return 0;
+    return wx_lattice_fold_matrix(cf, NS, NF, inverse != 0, m) ? NF : 0;
+}
+
 // the factorisation for other translation units (wx_lattice2d.hip): p[j], kap[j] (j < F/2), g0 = g^(+-L), g2 = g^(-+2)
 bool wx_lattice_coeffs(const WxFilt &filt, int L, bool inverse, double *p, double *kap, double *g0, double *g2)
 {
@@ -131,6 +190,24 @@ static int wx_lattice_launch(bool inverse, const double *x, double *y, int64_t n
     // wavefronts per SIMD the kernels are compiled for (amdgpu_waves_per_eu): the forward fits 3 (166 registers); the
     // inverse needs 194 registers without spills, and its spills at 3 cost 15 % extra HBM traffic (scratch) and 6 % time
     // (db4 L = 10: 0.84 ms at 3, 0.78 ms at 2; the forward built for 2 is 2 % slower than for 3)
+    // Full depth, 6 and more rotations: the inverse with its deepest levels folded (wx_lattice_fold.h), also for 2 wavefronts.
+    // k_lat_iwpt12_f64<NS, 2, 8> builds to 218 / 218 / 246 VGPRs and 106 / 106 / 102 SGPRs for NS = 6 / 8 / 10, no scratch and no
+    // spilled register, two wavefronts per SIMD like the general kernel (200 VGPRs, 58 SGPRs at NS = 8).  The compiler's summary is
+    // the only check there is: a spill would not fail the build.  Measured, config 2 inverse leg: 1.030 ms general, 0.977 / 0.936 /
+    // 0.910 ms with levels 12 / 11-12 / 10-12 folded (profiles/fold_cfg2.md)
+    if (inverse && L == 12 && wx_lat_stages(filt.F) >= 6 && !wx_lattice_no_fold()) {
+        WxLatFold<WX_LAT_FOLD> fm;
+        if (wx_lattice_fold_matrix(cf, wx_lat_stages(filt.F), WX_LAT_FOLD, true, fm.m)) {
+            switch (wx_lat_stages(filt.F)) {
+            case 6: hipLaunchKernelGGL((k_lat_iwpt12_f64<6, 2, WX_LAT_FOLD>), dim3((unsigned)grid), dim3(64), 0, st, x, y, batch, in_stride, cf, fm); break;
+            case 8: hipLaunchKernelGGL((k_lat_iwpt12_f64<8, 2, WX_LAT_FOLD>), dim3((unsigned)grid), dim3(64), 0, st, x, y, batch, in_stride, cf, fm); break;
+            default: hipLaunchKernelGGL((k_lat_iwpt12_f64<10, 2, WX_LAT_FOLD>), dim3((unsigned)grid), dim3(64), 0, st, x, y, batch, in_stride, cf, fm); break;
+            }
+            const hipError_t ef = hipGetLastError();
+            if (ef != hipSuccess) return wx_set_hip_error(ef, "lattice iwpt launch (folded)", __FILE__, __LINE__);
+            return 1;
+        }
+    }
 #define WX_GO(NSS)                                                                                                  \
     case NSS:                                                                                                       \
         if (inverse)                                                                                                \

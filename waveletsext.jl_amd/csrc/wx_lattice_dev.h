@@ -26,6 +26,10 @@
 // ds_read_b64 (maps derived and checked in tools/lattice_lds_maps.py).  No workgroup barrier anywhere: one wavefront
 // = one workgroup, ordering is wave-level.  Per signal and lane: F/2 * 64 * L FMAs (2560 for db4, L = 10), ~110
 // DPP moves for the halos, 256 LDS writes + 256 LDS reads, one 32 KiB read and one 32 KiB write of HBM.
+// Vector instructions per wavefront at F = 16 (db8), L = 12, counted on the GPU (profiles/r04_fp64_issue.txt, fold_cfg2.md): 6144 lattice FMAs in all three
+// kernels' arithmetic; executed 6785 by k_lat_iwpt_f64<8, 2>, 6753 by k_lat_wpt_f64<8, 3>, 7626 by k_lat_wpd_f64<8, 2>.  The full-depth
+// inverse of filters with 6 and more rotations folds levels 10-12 into one 8 x 8 matrix per node (wx_lattice_fold.h,
+// k_lat_iwpt12_f64<8, 2, 8>): 4608 lattice FMAs + 512 for the matrices, 5728 executed.
 //
 // Rounding: the rotations reassociate the reference's tap sums; measured difference from the oracle <= 3e-15
 // relative for every filter of the table at L = 12 (tools/lattice_proto.py), far inside the 1e-10 bar.
@@ -1273,28 +1277,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) 
 }
 
 // ---------------------------------------------------------------- inverse
-// the inverse transform of one 4096-sample signal up to the L0 arrangement of its samples (see lat_fwd_from_l0): `sink(f, o)` receives,
-// round by round (f = p[5:4]), the eight 16-byte pieces o[hi3] = samples p, p + 1 with p[11:9] = hi3, p[8:6] = lane >> 3, p[3:1] = lane & 7.
-// k_lat_iwpt_f64 stores them (eight complete lines per instruction); k_lat_iwpt8k_f64 keeps them as one child of an 8192-sample signal.
-template <int NS, typename TM, typename SINK>
-__device__ __forceinline__ void lat_inv_to_l0(const TM *__restrict__ xs, unsigned lds0, int lane, int L, const WxLat &cf, SINK &&sink)
+// second part of lat_inv_to_l0 (shared with the folding kernels of wx_lattice_fold.h): layout C after its levels -> B (levels 6-3) -> A
+// (levels 2-1) -> the L0 arrangement, handed to `sink`
+template <int NS, typename SINK>
+__device__ __forceinline__ void lat_inv_c_to_l0(double (&c)[64], unsigned lds0, int lane, const WxLat &cf, SINK &&sink)
 {
-    double c[64];
-    switch (L) {
-    case 6: lat_load_c<6>(c, lds0, xs, lane, cf); break;
-    case 7: lat_load_c<7>(c, lds0, xs, lane, cf); break;
-    case 8: lat_load_c<8>(c, lds0, xs, lane, cf); break;
-    case 9: lat_load_c<9>(c, lds0, xs, lane, cf); break;
-    case 10: lat_load_c<10>(c, lds0, xs, lane, cf); break;
-    case 11: lat_load_c<11>(c, lds0, xs, lane, cf); break;
-    default: lat_load_c<12>(c, lds0, xs, lane, cf); break;
-    }
-    if (L > 11) lat_level<5, 0, NS, true>(c, cf);
-    if (L > 10) lat_level<4, 0, NS, true>(c, cf);
-    if (L > 9) lat_level<3, 0, NS, true>(c, cf);
-    if (L > 8) lat_level<2, 0, NS, true>(c, cf);
-    if (L > 7) lat_level<1, 0, NS, true>(c, cf);
-    if (L > 6) lat_level<0, 0, NS, true>(c, cf);
     // T3i: C -> B
     double bb[64];
     {
@@ -1354,6 +1341,31 @@ __device__ __forceinline__ void lat_inv_to_l0(const TM *__restrict__ xs, unsigne
     lat_level<1, 6, NS, true>(a, cf);
     lat_level<0, 6, NS, true>(a, cf);
     lat_t1i(a, lds0, lane, sink);
+}
+
+// the inverse transform of one 4096-sample signal up to the L0 arrangement of its samples (see lat_fwd_from_l0): `sink(f, o)` receives,
+// round by round (f = p[5:4]), the eight 16-byte pieces o[hi3] = samples p, p + 1 with p[11:9] = hi3, p[8:6] = lane >> 3, p[3:1] = lane & 7.
+// k_lat_iwpt_f64 stores them (eight complete lines per instruction); k_lat_iwpt8k_f64 keeps them as one child of an 8192-sample signal.
+template <int NS, typename TM, typename SINK>
+__device__ __forceinline__ void lat_inv_to_l0(const TM *__restrict__ xs, unsigned lds0, int lane, int L, const WxLat &cf, SINK &&sink)
+{
+    double c[64];
+    switch (L) {
+    case 6: lat_load_c<6>(c, lds0, xs, lane, cf); break;
+    case 7: lat_load_c<7>(c, lds0, xs, lane, cf); break;
+    case 8: lat_load_c<8>(c, lds0, xs, lane, cf); break;
+    case 9: lat_load_c<9>(c, lds0, xs, lane, cf); break;
+    case 10: lat_load_c<10>(c, lds0, xs, lane, cf); break;
+    case 11: lat_load_c<11>(c, lds0, xs, lane, cf); break;
+    default: lat_load_c<12>(c, lds0, xs, lane, cf); break;
+    }
+    if (L > 11) lat_level<5, 0, NS, true>(c, cf);
+    if (L > 10) lat_level<4, 0, NS, true>(c, cf);
+    if (L > 9) lat_level<3, 0, NS, true>(c, cf);
+    if (L > 8) lat_level<2, 0, NS, true>(c, cf);
+    if (L > 7) lat_level<1, 0, NS, true>(c, cf);
+    if (L > 6) lat_level<0, 0, NS, true>(c, cf);
+    lat_inv_c_to_l0<NS>(c, lds0, lane, cf, sink);
 }
 
 template <int NS, int WPE, typename TM = double>
