@@ -488,6 +488,60 @@ int wx_isiwpd_f32(float *W, const uint8_t *status, float *xh, int64_t n, int L, 
                   int F, int literal, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * WaveMult -- the Beylkin-Coifman-Rokhlin standard and non-standard forms of an operator and their products with a
+ * batch of vectors (wavemult/utils.jl, transforms.jl, mat2sparse.jl, wavemult.jl).  Signals are columns, batch last.
+ * wx_ns_dwt1d_*   ns_dwt(x, wt, L) transforms.jl:52-70 for every column of x (n, batch) -> nxw (2n, batch): level l keeps
+ *                 s_l in ndyad(l, Lmax, false) and d_l in ndyad(l, Lmax, true) (utils.jl:146-155), nxw[1:2^(Lmax-L)] = s_L,
+ *                 every other position is 0.  WX_EASSERT unless n = 2^Lmax and 1 <= L <= Lmax (:57-58).
+ * wx_ns_idwt1d_*  ns_idwt(nxw, wt, L) transforms.jl:124-142, nxw (2n, batch) -> x (n, batch); not the inverse of ns_dwt.
+ * wx_sft_*        sft(M, wt, L) transforms.jl:171-185 (inverse = 0) / isft(Mw, wt, L) :214-228 (inverse != 0) of M (n, m);
+ *                 WX_EASSERT unless 1 <= L <= maxtransformlevels(M) (:174, 217); both sides dyadic.
+ * wx_sparseform_count_* / wx_sparseform_fill_*: the two halves of mat2sparseform_std (mat2sparse.jl:89-100, L_nonstd = 0, Mw =
+ *                 sft(M): N = n columns) and mat2sparseform_nonstd (:38-55, L_nonstd = L >= 1, Mw = dwt(M, wt, L), the 2-D pyramid:
+ *                 the indices pass through stretchmatrix, utils.jl:98-114, N = 2n columns; WX_EASSERT as stretchmatrix asserts, :101).
+ *                 count: thr = T(eps) * max_j norm(Mw[:, j]) goes to thr_out (one value), colptr receives Julia's 1-based column
+ *                 pointers (N + 1 values) of the entries with abs(Mw) > thr -- strict, exact zeros are never stored.  The caller
+ *                 allocates rowval / nzval with colptr[N+1] - 1 entries; fill writes them (1-based rows, ascending inside a column)
+ *                 for the same Mw and thr.  Mw (n, n).  Pointers may be host or device.
+ * wx_wavemult_plan_create_*: takes the three arrays of a SparseMatrixCSC{T,Int64} of size N x N as Julia holds them (host or
+ *                 device) and builds the row-oriented device layout of the product once; *plan is an opaque handle like
+ *                 wx_comm_init's, owned by the caller: wx_shutdown() does not release it, wx_wavemult_plan_destroy does.
+ *                 The call returns with the stream idle.  WX_EARG for arrays that are not a CSC matrix.
+ * wx_wavemult_apply_*: nonstd = 0: y = idwt(SM * dwt(x, wt, L), wt, L), std_wavemult(SM, x, wt, L) wavemult.jl:143-152;
+ *                 nonstd != 0: y = ns_idwt(NM * ns_dwt(x, wt, L), wt, L), nonstd_wavemult(NM, x, wt, L) :67-76; x, y (n, batch),
+ *                 three launches through stream-ordered scratch.  WX_EASSERT unless N == (nonstd ? 2n : n), n = 2^Lmax and
+ *                 L <= Lmax (1 <= L for the non-standard form).  Every element of the product is summed by one lane in ascending
+ *                 column order, without atomics: two applications of a plan give identical bits.
+ * wx_wavemult_product_*: the middle step alone, Y (N, batch) = A X (N, batch) for the plan's N x N matrix A (SparseArrays' A * X); Y must not be X.
+ * wx_wavemult_plan_info: info[0..7] = N, stored entries, padded entries, slices, rows cut into pieces, longest piece, bytes of the
+ *                 layout, signals per workgroup.
+ * ------------------------------------------------------------------------------------------ */
+int wx_ns_dwt1d_f64(const double *x, double *nxw, int64_t n, int L, int64_t batch, const double *qmf, int F, void *stream);
+int wx_ns_dwt1d_f32(const float *x, float *nxw, int64_t n, int L, int64_t batch, const double *qmf, int F, void *stream);
+int wx_ns_idwt1d_f64(const double *nxw, double *x, int64_t n, int L, int64_t batch, const double *qmf, int F, void *stream);
+int wx_ns_idwt1d_f32(const float *nxw, float *x, int64_t n, int L, int64_t batch, const double *qmf, int F, void *stream);
+int wx_sft_f64(const double *M, double *Mw, int64_t n, int64_t m, int L, int inverse, const double *qmf, int F, void *stream);
+int wx_sft_f32(const float *M, float *Mw, int64_t n, int64_t m, int L, int inverse, const double *qmf, int F, void *stream);
+int wx_sparseform_count_f64(const double *Mw, int64_t n, int L_nonstd, double eps, int64_t *colptr, double *thr_out, void *stream);
+int wx_sparseform_count_f32(const float *Mw, int64_t n, int L_nonstd, double eps, int64_t *colptr, float *thr_out, void *stream);
+int wx_sparseform_fill_f64(const double *Mw, int64_t n, int L_nonstd, double thr, const int64_t *colptr, int64_t *rowval,
+                           double *nzval, void *stream);
+int wx_sparseform_fill_f32(const float *Mw, int64_t n, int L_nonstd, double thr, const int64_t *colptr, int64_t *rowval,
+                           float *nzval, void *stream);
+int wx_wavemult_plan_create_f64(const int64_t *colptr, const int64_t *rowval, const double *nzval, int64_t N, void **plan,
+                                void *stream);
+int wx_wavemult_plan_create_f32(const int64_t *colptr, const int64_t *rowval, const float *nzval, int64_t N, void **plan,
+                                void *stream);
+int wx_wavemult_apply_f64(const void *plan, int nonstd, const double *x, double *y, int64_t n, int L, int64_t batch,
+                          const double *qmf, int F, void *stream);
+int wx_wavemult_apply_f32(const void *plan, int nonstd, const float *x, float *y, int64_t n, int L, int64_t batch,
+                          const double *qmf, int F, void *stream);
+int wx_wavemult_product_f64(const void *plan, const double *X, double *Y, int64_t batch, void *stream);
+int wx_wavemult_product_f32(const void *plan, const float *X, float *Y, int64_t batch, void *stream);
+int wx_wavemult_plan_info(const void *plan, int64_t *info);
+int wx_wavemult_plan_destroy(void *plan);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU exchange (one process per GPU, RCCL over xGMI; bound lazily, single-GPU callers never
  * load RCCL).  Transforms shard over the batch (last) dimension with no collective: the loops
  * dwt/dwt_all.jl:277-279, swt/swt_all.jl:171-173, acwt/acwt_all.jl:254-256 are independent per

@@ -36,6 +36,9 @@ from .ldb import (TimeFrequency, AsymmetricRelativeEntropy, SymmetricRelativeEnt
 from .siwt import (ShiftInvariantWaveletTransformNode, ShiftInvariantWaveletTransformObject,               # noqa: F401,E402
                    ShiftInvariantWaveletTransformBatch, siwpd, siwpdall, isiwpd, isiwpdall, bestbasistree_,
                    bestbasistreeall_, delete_node_)
+from .wavemult import (SparseMatrixCSC, dyadlength, stretchmatrix, ndyad, ns_dwt, ns_idwt, ns_dwtall, ns_idwtall, sft, isft,   # noqa: F401,E402
+                       mat2sparseform_std, mat2sparseform_nonstd, std_wavemult, nonstd_wavemult, std_wavemultall,
+                       nonstd_wavemultall)
 from . import siwt as _siwt                                                                                # noqa: E402
 _isvalidtree_arrays = isvalidtree                                                                          # noqa: F405
 

@@ -114,6 +114,14 @@ _EXTRA_SIGS = {
     "wx_siwpd": [_P, _P, _P, _L, _I, _I, _L, _P, _I, _P],
     "wx_siwt_bestbasis": [_P, _P, _I, _I, _L, _P],
     "wx_isiwpd": [_P, _P, _P, _L, _I, _I, _L, _P, _I, _I, _P],
+    "wx_ns_dwt1d": [_P, _P, _L, _I, _L, _P, _I, _P],
+    "wx_ns_idwt1d": [_P, _P, _L, _I, _L, _P, _I, _P],
+    "wx_sft": [_P, _P, _L, _L, _I, _I, _P, _I, _P],
+    "wx_sparseform_count": [_P, _L, _I, ctypes.c_double, _P, _P, _P],
+    "wx_sparseform_fill": [_P, _L, _I, ctypes.c_double, _P, _P, _P, _P],
+    "wx_wavemult_plan_create": [_P, _P, _P, _L, ctypes.POINTER(ctypes.c_void_p), _P],
+    "wx_wavemult_apply": [_P, _I, _P, _P, _L, _I, _L, _P, _I, _P],
+    "wx_wavemult_product": [_P, _P, _P, _L, _P],
 }
 _PLAIN_SIGS = {
     "wx_treeselect_f64": [_P, _L, _L, _I, _P],
@@ -170,6 +178,8 @@ _PLAIN_SIGS = {
     "wx_lsdb_costs2d_f32": [_P, _L, _L, _L, _L, _I, _P, _P],
     "wx_treeselect_batch_f64": [_P, _L, _L, _L, _I, _L, _P, _P],
     "wx_treeselect_batch_f32": [_P, _L, _L, _L, _I, _L, _P, _P],
+    "wx_wavemult_plan_info": [_P, _P],
+    "wx_wavemult_plan_destroy": [_P],
     "wx_comm_unique_id": [_P],
     "wx_comm_init": [_I, _I, _P, ctypes.POINTER(ctypes.c_void_p)],
     "wx_comm_destroy": [_P],

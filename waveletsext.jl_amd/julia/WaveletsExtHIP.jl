@@ -36,6 +36,8 @@ import WaveletsExt.BestBasis: tree_costs, JBB, BB, LSDB, LoglpCost, NormCost, Sh
                               DifferentialEntropyCost, bestbasis_treeselection, bestbasistreeall
 import WaveletsExt.Utils: getbasiscoef, getbasiscoefall
 import WaveletsExt.Denoising: surethreshold, relerrorthreshold
+import WaveletsExt.WaveMult: ns_dwt, ns_idwt, sft, isft, mat2sparseform_std, mat2sparseform_nonstd, std_wavemult, nonstd_wavemult
+using SparseArrays: SparseMatrixCSC
 import WaveletsExt.LDB: energy_map, discriminant_power, TimeFrequency, ProbabilityDensity, Signatures,
                         FishersClassSeparability, RobustFishersClassSeparability
 
@@ -856,6 +858,117 @@ function siwt_node(b::SIWTBatch{T}, sig::Integer, j::Integer, i::Integer, t::Int
     return WaveletsExt.SIWT.ShiftInvariantWaveletTransformNode{1,Int,T}(j, i, t,
         b.costs[siwt_nodeoff(j, b.d) + (slot << j) + i + 1, sig], v)
 end
+
+# ---------------------------------------------------------------------------------------------------------------------
+# WaveMult -- wavemult/transforms.jl, mat2sparse.jl, wavemult.jl (include/waveletsext_hip.h "WaveMult")
+# ---------------------------------------------------------------------------------------------------------------------
+# ns_dwt (transforms.jl:52-70) / ns_idwt (:124-142); the `all` forms take one signal per column
+function ns_dwt(x::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(x)) where T<:FT
+    n = length(x); nxw = newlike(x, T, (2n,)); q = qmfvec(wt)
+    check(wx_ns_dwt1d(T, raw(x), nxw, n, L, 1, q, length(q), stream()))
+    return nxw
+end
+function ns_idwt(nxw::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(nxw) - 1) where T<:FT
+    n = length(nxw) ÷ 2; x = newlike(nxw, T, (n,)); q = qmfvec(wt)
+    check(wx_ns_idwt1d(T, raw(nxw), x, n, L, 1, q, length(q), stream()))
+    return x
+end
+function ns_dwtall(x::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(size(x, 1))) where T<:FT
+    n, N = size(x); nxw = newlike(x, T, (2n, N)); q = qmfvec(wt)
+    check(wx_ns_dwt1d(T, raw(x), nxw, n, L, N, q, length(q), stream()))
+    return nxw
+end
+function ns_idwtall(nxw::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(size(nxw, 1)) - 1) where T<:FT
+    n = size(nxw, 1) ÷ 2; N = size(nxw, 2); x = newlike(nxw, T, (n, N)); q = qmfvec(wt)
+    check(wx_ns_idwt1d(T, raw(nxw), x, n, L, N, q, length(q), stream()))
+    return x
+end
+# sft (transforms.jl:171-185) / isft (:214-228)
+function sft(M::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(M)) where T<:FT
+    Mw = newlike(M, T, size(M)); q = qmfvec(wt)
+    check(wx_sft(T, raw(M), Mw, size(M, 1), size(M, 2), L, 0, q, length(q), stream()))
+    return Mw
+end
+function isft(Mw::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(Mw)) where T<:FT
+    M = newlike(Mw, T, size(Mw)); q = qmfvec(wt)
+    check(wx_sft(T, raw(Mw), M, size(Mw, 1), size(Mw, 2), L, 1, q, length(q), stream()))
+    return M
+end
+# the entries of Mw (n x n) above ϵ * the largest column norm as a SparseMatrixCSC; Lns >= 1 stretches (utils.jl:98-114)
+function sparseform(::Type{T}, Mw, n::Integer, Lns::Integer, ϵ::Real) where T<:FT
+    N = Lns == 0 ? n : 2n
+    colptr = Vector{Int64}(undef, N + 1); thr = Vector{T}(undef, 1)
+    check(wx_sparseform_count(T, Mw, n, Lns, ϵ, colptr, thr, stream()))
+    nnz = colptr[end] - 1
+    rowval = Vector{Int64}(undef, nnz); nzval = Vector{T}(undef, nnz)
+    check(wx_sparseform_fill(T, Mw, n, Lns, thr[1], colptr, rowval, nzval, stream()))
+    return SparseMatrixCSC{T,Int64}(N, N, colptr, rowval, nzval)
+end
+# mat2sparseform_std (mat2sparse.jl:89-100) / mat2sparseform_nonstd (:38-55)
+function mat2sparseform_std(M::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(M), ϵ::T = T(1e-4)) where T<:FT
+    @assert size(M, 1) == size(M, 2)
+    return sparseform(T, sft(M, wt, L), size(M, 1), 0, ϵ)
+end
+function mat2sparseform_nonstd(M::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(M), ϵ::T = T(1e-4)) where T<:FT
+    @assert size(M, 1) == size(M, 2)
+    @assert 1 ≤ L ≤ maxtransformlevels(M)
+    return sparseform(T, dwt(M, wt, L), size(M, 1), L, ϵ)
+end
+# the device layout of one sparse operator (wx_wavemult_plan_create): make it once, apply it to many batches, close it
+mutable struct WaveMultPlan{T}
+    handle::Ptr{Cvoid}
+    N::Int
+end
+function WaveMultPlan(A::SparseMatrixCSC{T,Int64}) where T<:FT
+    size(A, 1) == size(A, 2) || throw(ArgumentError("the operator must be square"))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(wx_wavemult_plan_create(T, A.colptr, A.rowval, A.nzval, size(A, 2), h, stream()))
+    p = WaveMultPlan{T}(h[], size(A, 2))
+    finalizer(close, p)
+    return p
+end
+function Base.close(p::WaveMultPlan)
+    h = p.handle; p.handle = C_NULL
+    h == C_NULL || check(wx_wavemult_plan_destroy(h))
+    return nothing
+end
+function plan_info(p::WaveMultPlan)
+    info = Vector{Int64}(undef, 8)
+    check(wx_wavemult_plan_info(p.handle, info))
+    return info
+end
+# A * X for the plan's matrix and one vector per column of X: the middle step alone
+function Base.:*(p::WaveMultPlan{T}, X::HIP{T}) where T<:FT
+    Y = newlike(X, T, size(X))
+    check(wx_wavemult_product(T, p.handle, raw(X), Y, length(X) ÷ p.N, stream()))
+    return Y
+end
+# y = idwt(SM * dwt(x)) / ns_idwt(NM * ns_dwt(x)) for one vector or one vector per column
+function wavemult(p::WaveMultPlan{T}, nonstd::Bool, x::HIP{T}, wt::OrthoFilter, L::Integer) where T<:FT
+    n = size(x, 1); y = newlike(x, T, size(x)); q = qmfvec(wt)
+    check(wx_wavemult_apply(T, p.handle, nonstd, raw(x), y, n, L, length(x) ÷ n, q, length(q), stream()))
+    return y
+end
+function wavemult(A::SparseMatrixCSC{T,Int64}, nonstd::Bool, x::HIP{T}, wt::OrthoFilter, L::Integer) where T<:FT
+    p = WaveMultPlan(A)
+    y = wavemult(p, nonstd, x, wt, L)
+    close(p)
+    return y
+end
+# std_wavemult (wavemult.jl:134-152) / nonstd_wavemult (:58-76)
+std_wavemult(SM::SparseMatrixCSC{T,Int64}, x::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(x)) where T<:FT =
+    wavemult(SM, false, x, wt, L)
+nonstd_wavemult(NM::SparseMatrixCSC{T,Int64}, x::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(x)) where T<:FT =
+    wavemult(NM, true, x, wt, L)
+std_wavemult(M::AbstractMatrix{T}, x::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(x), ϵ::T = T(1e-4)) where T<:FT =
+    wavemult(mat2sparseform_std(HIP(M), wt, L, ϵ), false, x, wt, L)
+nonstd_wavemult(M::AbstractMatrix{T}, x::HIP{T,1}, wt::OrthoFilter, L::Integer = maxtransformlevels(x), ϵ::T = T(1e-4)) where T<:FT =
+    wavemult(mat2sparseform_nonstd(HIP(M), wt, L, ϵ), true, x, wt, L)
+# a batch of vectors (n, N) with one operator: pass the plan to keep the layout across calls
+std_wavemultall(A::Union{WaveMultPlan{T},SparseMatrixCSC{T,Int64}}, X::HIP{T,2}, wt::OrthoFilter,
+                L::Integer = maxtransformlevels(size(X, 1))) where T<:FT = wavemult(A, false, X, wt, L)
+nonstd_wavemultall(A::Union{WaveMultPlan{T},SparseMatrixCSC{T,Int64}}, X::HIP{T,2}, wt::OrthoFilter,
+                   L::Integer = maxtransformlevels(size(X, 1))) where T<:FT = wavemult(A, true, X, wt, L)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # multi-GPU (one process per GPU; include/waveletsext_hip.h "Multi-GPU exchange")
