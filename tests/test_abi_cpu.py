@@ -218,6 +218,37 @@ def test_redundant2d_argument_errors(wx):
     assert lib.wx_iacwpd2d_f64(p, p, i64(8), i64(16), i64(5), ci(0), fp, i64(21), i64(1), None) == EBOUNDS
 
 
+def test_swt1d_debug_entry_points_refuse_bad_arguments(wx):
+    """csrc/wx_debug.h: the launch record and the schedule query of the 1-D redundant transforms, at the C level (no device)"""
+    lib = ctypes.CDLL(wx.LIB_PATH)
+    EARG = -2
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    lib.wx_debug_swt1d_trace_dropped.restype = i64
+    row = (ctypes.c_int32 * 11)()
+    assert lib.wx_debug_swt1d_trace_end(row, ci(1)) == EARG                     # end without begin
+    lib.wx_debug_swt1d_trace_begin()
+    assert lib.wx_debug_swt1d_trace_end(row, ci(0)) == EARG                     # cap = 0: refused, the record stays armed
+    assert lib.wx_debug_swt1d_trace_end(None, ci(4)) == EARG
+    assert lib.wx_debug_swt1d_trace_end(row, ci(1)) == 0                        # nothing was launched
+    assert lib.wx_debug_swt1d_trace_dropped() == 0
+    assert lib.wx_debug_swt1d_trace_end(row, ci(1)) == EARG                     # that end disarmed it
+    with wx.swt1d_trace() as tr:
+        pass
+    assert list(tr) == [] and tr.dropped == 0
+    assert set(wx.SWT1D_ROUTES) == set(range(1, 20)) and len(set(wx.SWT1D_ROUTES.values())) == 19
+    out = (ctypes.c_int32 * (4 * 24))()
+    plan = lambda layout, L, F, sm, n, es: lib.wx_debug_swt_inv_plan(ci(layout), ci(L), ci(F), i64(sm), i64(n), ci(es), ci(0), ci(0), out)
+    assert plan(1, 3, 8, -1, 0, 8) == EARG                                      # n = 0
+    assert plan(1, 7, 8, -1, 64, 8) == EARG                                     # wpt: more levels than the length admits
+    assert plan(1, 3, 8, -1, 64, 2) == EARG                                     # no such element type
+    assert plan(3, 3, 8, -1, 64, 8) == EARG and plan(1, -1, 8, -1, 64, 8) == EARG and plan(1, 25, 8, -1, 1 << 26, 8) == EARG
+    assert lib.wx_debug_swt_inv_plan(ci(1), ci(3), ci(8), i64(-1), i64(64), ci(8), ci(0), ci(0), None) == EARG
+    assert plan(0, 3, 8, -1, 64, 8) == 3 and list(out[:12]) == [3, 2, 0, 1, 2, 1, 0, 1, 1, 0, 0, 1]
+    assert plan(1, 0, 8, -1, 64, 8) == 0
+    with pytest.raises(wx.ArgumentError):
+        wx.swt_inv_plan("wpt", 3, 8, 0, 8)
+
+
 def test_header_compiles_as_c_and_example_links(tmp_path, wx):
     """include/waveletsext_hip.h is a C header: examples/roundtrip.c builds with gcc -std=c99 against the .so
     (and, without a GPU, fails loudly with the library's status instead of computing on the CPU)"""

@@ -23,8 +23,13 @@ def test_config3_geometry_swpt_iswpt(wx, oracle):
     n, L, B = 16384, 12, 2
     x = np.asfortranarray(rng.standard_normal((n, B)))
     xd = wx.to_device(x)
-    xw = wx.swptall(xd, wt, L)                                        # (n, 4096, B): 1 GiB on the device
+    with wx.swt1d_trace() as tr:
+        xw = wx.swptall(xd, wt, L)                                    # (n, 4096, B): 1 GiB on the device
     assert tuple(xw.shape) == (n, 1 << L, B)
+    # launch record (csrc/wx_debug.h): two three-level composite passes over whole columns, then the Haar register pass over the
+    # last six levels
+    fwd = [(t.route, t.depth, t.K, t.R, t.OPT) for t in tr]
+    assert fwd == [("FM", 0, 3, 0, 0), ("FM", 3, 3, 0, 0), ("FHAAR6", 6, 6, 0, 0)], fwd
     for b in range(B):
         ref = oracle.swpt(x[:, b], wt.qmf, L)
         got = xw[:, :, b].cpu().numpy()
@@ -35,8 +40,13 @@ def test_config3_geometry_swpt_iswpt(wx, oracle):
             refd = wx.to_device(np.asfortranarray(ref[:, :, None]))
             back = wx.iswptall(refd, wt)
             assert relerr(back[:, 0].cpu().numpy(), back_ref) <= 1e-10
-    xr = wx.iswptall(xw, wt)
+    with wx.swt1d_trace() as tr:
+        xr = wx.iswptall(xw, wt)
     assert float((xr - xd).abs().max()) <= 1e-10
+    # the Haar register pass over the deepest five levels, one fused two-level pass, then the top five levels out of LDS tiles
+    inv = [(t.route, t.depth, t.K, t.R, t.OPT) for t in tr]
+    assert inv == [("IHAAR6", 12, 5, 0, 0), ("IM", 7, 2, 8, 8)] + [("ITILE", d, 1, 1, 0) for d in (5, 4, 3, 2, 1)], inv
+    assert wx.swt_inv_plan("wpt", L, 2, n, 8, haar6=True) == [(12, 7, 64, 0), (7, 5, 8, 8)] + [(d, d - 1, 0, 1) for d in (5, 4, 3, 2, 1)]
     del xw, xr
     torch.cuda.empty_cache()
 

@@ -4,6 +4,8 @@ The product path has NO CPU fallback: if the shared library is missing this modu
 import of the symbol table, and every compute entry point fails with WxError(WX_EHIP) when no
 HIP device is visible.
 """
+import collections
+import contextlib
 import ctypes
 import os
 
@@ -48,6 +50,14 @@ def _declare(L):
     L.wx_debug_set_dispatch.restype = None
     L.wx_debug_red2d_route.argtypes = [_I, _L, _L, _I, _I, _I, _I, _I]
     L.wx_debug_red2d_route.restype = _I
+    L.wx_debug_swt1d_trace_begin.argtypes = []
+    L.wx_debug_swt1d_trace_begin.restype = None
+    L.wx_debug_swt1d_trace_end.argtypes = [_P, _I]
+    L.wx_debug_swt1d_trace_end.restype = _I
+    L.wx_debug_swt1d_trace_dropped.argtypes = []
+    L.wx_debug_swt1d_trace_dropped.restype = _L
+    L.wx_debug_swt_inv_plan.argtypes = [_I, _I, _I, _L, _L, _I, _I, _I, _P]
+    L.wx_debug_swt_inv_plan.restype = _I
     sigs = {
         # name: argtypes (without the _f64/_f32 suffix)
         "wx_wpd1d": [_P, _P, _L, _I, _L, _P, _I, _P],
@@ -254,3 +264,48 @@ def red2d_route(inverse, m, n, L, elem_size, F, ac=False, shift=False):
     if code < 0:
         raise ValueError("wx_debug_red2d_route: arguments outside the transforms' domain")
     return RED2D_ROUTES[code & 255], code >> 8
+
+
+# csrc/wx_debug.h: route ids of the 1-D redundant transforms' launch record
+SWT1D_ROUTES = {1: "FG", 2: "FSD", 3: "FSDIP", 4: "FTWO", 5: "FLVL", 6: "FM", 7: "FMRC", 8: "FHAAR6", 9: "FDEEP",
+                10: "ISD", 11: "ISDIP", 12: "IM", 13: "IHAAR6", 14: "IDEEP", 15: "ITILE", 16: "ILVL",
+                17: "IACDWT", 18: "IACWPT", 19: "IACWPD"}
+SWT1D_TRACE_MAX = 1 << 18
+Swt1dLaunch = collections.namedtuple("Swt1dLaunch", "route depth K R OPT elem_size block grid_x grid_y grid_z lds")
+
+
+class Swt1dTrace(list):
+    """the list `swt1d_trace` yields; `dropped` = launches past SWT1D_TRACE_MAX, which the record does not hold"""
+    dropped = 0
+
+
+@contextlib.contextmanager
+def swt1d_trace():
+    """Record every kernel launch of the 1-D redundant transforms made inside the block (csrc/wx_debug.h:
+    wx_debug_swt1d_trace_begin / _end; process-global, so one block at a time).  Yields a list that holds one Swt1dLaunch per
+    launch, in launch order, once the block has ended."""
+    import numpy as np
+    L = lib()
+    out = Swt1dTrace()
+    L.wx_debug_swt1d_trace_begin()
+    try:
+        yield out
+    finally:
+        buf = np.empty((SWT1D_TRACE_MAX, len(Swt1dLaunch._fields)), dtype=np.int32)
+        got = L.wx_debug_swt1d_trace_end(buf.ctypes.data, SWT1D_TRACE_MAX)
+        check(min(got, 0))
+        out.dropped = int(L.wx_debug_swt1d_trace_dropped())
+        for row in buf[:got].tolist():
+            out.append(Swt1dLaunch(SWT1D_ROUTES[row[0]], *row[1:]))
+
+
+def swt_inv_plan(layout, L, F, n, elem_size, sm=None, has_tree=False, haar6=False):
+    """[(from, to, R, OPT)] of every pass of the 1-D redundant inverse under the current dispatch mode (csrc/wx_debug.h:
+    wx_debug_swt_inv_plan, which runs the launcher's own wx_swt_inv_plan; needs no device).  layout "dwt" / "wpt" / "wpd"."""
+    import numpy as np
+    out = np.zeros((max(int(L), 1), 4), dtype=np.int32)
+    code = {"dwt": 0, "wpt": 1, "wpd": 2}.get(layout, layout)
+    got = lib().wx_debug_swt_inv_plan(int(code), int(L), int(F), -1 if sm is None else int(sm), int(n), int(elem_size),
+                                      int(bool(has_tree)), int(bool(haar6)), out.ctypes.data)
+    check(min(got, 0))
+    return [tuple(r) for r in out[:got].tolist()]

@@ -26,6 +26,49 @@ int wx_debug_lattice_fold(const double *q, int F, int NF, int inverse, double *m
  * R is the strip height of the deepest level (depth L - 1) for F1, F2 and I1, and 0 for the other routes.  Mode 1 of
  * wx_debug_set_dispatch turns F1 / F2 into F3 and I1 into I2. */
 int wx_debug_red2d_route(int inverse, int64_t m, int64_t n, int L, int elem_size, int F, int ac, int shift);
+
+/* Launch record of the 1-D redundant transforms (wx_swt1d.hip, wx_haarswt.hip, wx_swtdeep*.hip): between _begin and _end every
+ * kernel launch of wx_dev_swt_fwd, wx_dev_swt_inv, wx_dev_iacdwt / _iacwpt / _iacwpd and of the Haar and lane-local register
+ * passes appends one row, written next to the launch from the variables the launch uses.  The record is process-global and
+ * mutex-protected; disarmed, a launch site pays one load of a flag.  The fused acwpd + moments path (wx_dev_acwpd_top_moments,
+ * wx_acsubtree.hip) is not recorded.  A row is WX_SWT1D_TRACE_FIELDS int32:
+ *     route, depth, K, R, OPT, elem_size, blockDim.x, gridDim.x, gridDim.y, gridDim.z, dynamic LDS bytes
+ * depth = the depth the pass starts from (forward: the parents' depth; inverse: the children's depth), K = levels in the pass.
+ * R and OPT are the residue classes per workgroup and the rows per thread of FMRC and IM; the other routes keep their own
+ * extras there (0 where none is named):
+ *   forward                                                             R                              OPT
+ *     1  FG      k_swt_fwd_level_g, one level from global memory                                       1 = autocorrelation
+ *     2  FSD     k_sdwt_fused, all K = L levels                         compile-time taps, 0 = runtime  1 = autocorrelation
+ *     3  FSDIP   k_sdwt_fused_ip, all K = L levels in place             compile-time taps, 0 = runtime  1 = autocorrelation
+ *     4  FTWO    k_swpd_fwd_two, K = 2                                                                  1 = autocorrelation
+ *     5  FLVL    k_swt_fwd_level, K = 1                                                                 1 = autocorrelation
+ *     6  FM      k_swt_fwd_multi, whole columns, K = 2 or 3
+ *     7  FMRC    k_swt_fwd_multi_rc, K = 2 or 3                         classes per workgroup           rows per thread
+ *     8  FHAAR6  k_haar_swpt6_fwd, K = 6
+ *     9  FDEEP   lane-local pass, K = LP                                1 = heap table (swpd / acwpd)   1 = autocorrelation
+ *   inverse
+ *    10  ISD     k_isdwt_avg_fused, all K = L levels                    compile-time taps, 0 = runtime  1 = pipelined
+ *    11  ISDIP   k_isdwt_avg_fused_ip, all K = L levels in place
+ *    12  IM      k_swt_inv_multi, K = 2 or 3                            classes per workgroup           rows per thread
+ *    13  IHAAR6  k_haar_iswpt, K = wx_haar_iswpt_levels()
+ *    14  IDEEP   lane-local pass, K = LP
+ *    15  ITILE   k_swt_inv_level_tile, K = 1                            HF = taps / 2
+ *    16  ILVL    k_swt_inv_level, K = 1                                                                 1 = shift based
+ *    17  IACDWT  18  IACWPT  19  IACWPD   k_iacdwt / k_iacwpt / k_iacwpd, all K = L levels
+ * _end disarms, copies the first min(cap, recorded) rows to out and returns the number recorded, which is at most
+ * WX_SWT1D_TRACE_MAX: launches past that are counted by _dropped (until the next _begin) and not recorded.  _end returns
+ * WX_EARG (-2) without _begin before it, or (leaving the record armed) for out == NULL or cap <= 0. */
+#define WX_SWT1D_TRACE_FIELDS 11
+#define WX_SWT1D_TRACE_MAX (1 << 18)
+void wx_debug_swt1d_trace_begin(void);
+int wx_debug_swt1d_trace_end(int32_t *out, int cap);
+int64_t wx_debug_swt1d_trace_dropped(void);
+
+/* The schedule of the 1-D redundant inverse (wx_swt_inv_plan, the function wx_swt1d's caller runs) under the current dispatch mode;
+ * needs no device.  layout 0 / 1 / 2 = dwt / wpt / wpd container, sm < 0 = average based, haar6 = the caller's wx_haar_swpt6_ok.
+ * out receives from, to, R, OPT of every pass (4 * L values at most; OPT = 0 marks the Haar register pass, -1 the lane-local one);
+ * returns the number of passes, or WX_EARG (-2) for n < 1, L outside 0..24 (wpt: 2^L > n), F < 2, another layout or element size. */
+int wx_debug_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, int elem_size, int has_tree, int haar6, int32_t *out);
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@
 // Applies to Float64, q[0] == q[1], the wpt layout, L >= 12 (dilation of the pass >= 64), average-based inverse.
 #include "wx_common.h"
 #include "wx_kernels.h"
+#include "wx_swt1d_trace.h"
 #include <cstdlib>
 
 namespace {
@@ -241,6 +242,7 @@ int wx_haar_swpt6_fwd(double *xw, int64_t n, int L, int64_t batch, const WxFilt 
     const int64_t blocks = ((int64_t)1 << d0) * (((int64_t)1 << d0) >> 6);
     int64_t gy = batch > 65535 ? 65535 : batch;
     // steps per loop iteration: 1 measured best (7.0 ms per 32 GiB; 8.1 at 2, 11.8 at 4: the unrolled bodies spill)
+    WX_SWT1D_TRACE(WX_RT_FHAAR6, d0, 6, 0, 0, sizeof(double), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0);
     hipLaunchKernelGGL(k_haar_swpt6_fwd<1>, dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, xw, (int)n, 1 << L, batch, d0, gain);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "haar swpt6 launch", __FILE__, __LINE__);
@@ -261,6 +263,7 @@ int wx_haar_iswpt6(const double *src, int64_t src_cols, double *dst, int64_t dst
     // profiles/r06_cfg3_inverse.txt: six consecutive processes each -- order 1 is 1-2 % faster in every placement of the table (6.88 / 7.47 /
     // 8.12 ms against 7.03 / 7.58 / 8.19), residency 2 the same as 3, 4 (spills) 18 ms; the spread itself follows the process sequence
     // whatever the order or the residency: it is the physical placement of the 32 GiB table (profiles/r05_cfg3_inverse.md)
+    WX_SWT1D_TRACE(WX_RT_IHAAR6, L, K, 0, 0, sizeof(double), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0);
     hipLaunchKernelGGL((k_haar_iswpt<K, 1, 1, 0>), dim3((unsigned)blocks, (unsigned)gy), dim3(64), 0, st, src, src_cols, dst, dst_cols,
                        (int)n, batch, d0, gain);
     const hipError_t e = hipGetLastError();

@@ -24,8 +24,11 @@
 #include "wx_common.h"
 #include "wx_kernels.h"
 #include "wx_host.h"
+#include "wx_swt1d_trace.h"
+#include "wx_debug.h"
 #include <cstdlib>
 #include <map>
+#include <mutex>
 #include <vector>
 
 int wx_force_generic();
@@ -1295,6 +1298,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
             const int nodes = layout == WX_LAYOUT_DWT ? 1 : (1 << d);
             const T *ain = (inplace_layout && d > 0) ? alt[(d - 1) & 1] : nullptr;
             T *aout = (inplace_layout && d + 1 < L) ? alt[d & 1] : nullptr;
+            WX_SWT1D_TRACE(WX_RT_FG, d, 1, 0, ac ? 1 : 0, sizeof(T), dim3(tiles, (unsigned)nodes, (unsigned)(batch > 1024 ? 1024 : batch)), dim3(256), 0);
             hipLaunchKernelGGL(kg, dim3(tiles, (unsigned)nodes, (unsigned)(batch > 1024 ? 1024 : batch)), dim3(256), 0, st, x, xw,
                                (int)n, ncols, batch, L, d, layout, filt, acz, ain, aout, alt_nc);
         }
@@ -1323,6 +1327,8 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         if (per_cu > 8) per_cu = 8;
         int64_t grid = (int64_t)256 * per_cu;
         if (grid > batch) grid = batch;
+        WX_SWT1D_TRACE(WX_RT_FSD, 0, L, kf == (ac ? (KF)k_sdwt_fused<T, true, 0> : (KF)k_sdwt_fused<T, false, 0>) ? 0 : filt.F, ac ? 1 : 0, sizeof(T),
+                       dim3((unsigned)grid), dim3(nt), 2 * lds);
         hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(nt), 2 * lds, st, x, xw, (int)n, batch, L, filt, acz, wx_sdwt_window_min_for(filt.F));
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
@@ -1341,6 +1347,8 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int64_t grid = 256;
         if (grid > batch) grid = batch;
+        WX_SWT1D_TRACE(WX_RT_FSDIP, 0, L, ki == (ac ? (KFI)k_sdwt_fused_ip<T, true, NPT, 0> : (KFI)k_sdwt_fused_ip<T, false, NPT, 0>) ? 0 : filt.F, ac ? 1 : 0,
+                       sizeof(T), dim3((unsigned)grid), dim3(1024), lds);
         hipLaunchKernelGGL(ki, dim3((unsigned)grid), dim3(1024), lds, st, x, xw, (int)n, batch, L, filt, acz);
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
@@ -1369,6 +1377,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
             if (3 * lds > 64 * 1024)
                 WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k2), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)(3 * lds)));
+            WX_SWT1D_TRACE(WX_RT_FTWO, d, 2, 0, ac ? 1 : 0, sizeof(T), dim3(1 << d, (unsigned)gy), dim3(nt), 3 * lds);
             hipLaunchKernelGGL(k2, dim3(1 << d, (unsigned)gy), dim3(nt), 3 * lds, st, x, xw, (int)n, ncols, batch, d, filt, acz);
             d += 2;
             continue;
@@ -1376,6 +1385,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         if (K == 1) {
             const int nodes = layout == WX_LAYOUT_DWT ? 1 : (1 << d);
             // long signals occupy most of a CU's LDS (one workgroup per CU): give that workgroup 16 waves
+            WX_SWT1D_TRACE(WX_RT_FLVL, d, 1, 0, ac ? 1 : 0, sizeof(T), dim3(nodes, (unsigned)gy), dim3(nt), lds);
             hipLaunchKernelGGL(kern, dim3(nodes, (unsigned)gy), dim3(nt), lds, st, x, xw, (int)n, ncols, batch, L, d,
                                layout, filt, acz);
             d += 1;
@@ -1443,6 +1453,8 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
             KM kr = nullptr;
             if (K == 2) kr = OPTrc == 8 ? k_swt_fwd_multi_rc<T, 4, 8> : OPTrc == 4 ? k_swt_fwd_multi_rc<T, 4, 4> : OPTrc == 2 ? k_swt_fwd_multi_rc<T, 4, 2> : k_swt_fwd_multi_rc<T, 4, 1>;
             else kr = OPTrc == 8 ? k_swt_fwd_multi_rc<T, 8, 8> : OPTrc == 4 ? k_swt_fwd_multi_rc<T, 8, 4> : OPTrc == 2 ? k_swt_fwd_multi_rc<T, 8, 2> : k_swt_fwd_multi_rc<T, 8, 1>;
+            WX_SWT1D_TRACE(WX_RT_FMRC, d, K, Rrc, OPTrc, sizeof(T), dim3((unsigned)(((int64_t)1 << d) * (sdil / Rrc)), (unsigned)gy), dim3(NT),
+                           (size_t)tile * sizeof(T));
             hipLaunchKernelGGL(kr, dim3((unsigned)(((int64_t)1 << d) * (sdil / Rrc)), (unsigned)gy), dim3(NT),
                                (size_t)tile * sizeof(T), st, x, xw, (int)n, ncols, batch, L, d, K, Rrc,
                                (const double *)dcoef, (const int *)dshift, Uc);
@@ -1462,6 +1474,7 @@ int wx_dev_swt_fwd(const T *x, T *xw, int64_t n, int L, int layout, int64_t batc
         if (lds > 64 * 1024)
             WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(km),
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        WX_SWT1D_TRACE(WX_RT_FM, d, K, 0, 0, sizeof(T), dim3(1 << d, (unsigned)gy), dim3(nt), lds);
         hipLaunchKernelGGL(km, dim3(1 << d, (unsigned)gy), dim3(nt), lds, st, x, xw, (int)n, ncols, batch, L, d, K,
                            (const double *)dcoef, (const int *)dshift, U);
         d += K;
@@ -1562,6 +1575,8 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
         int64_t grid = (int64_t)256 * per_cu;
         if (grid > batch) grid = batch;
+        WX_SWT1D_TRACE(WX_RT_ISD, L, L, ki == (pipe ? (KI)k_isdwt_avg_fused<T, 0, true> : (KI)k_isdwt_avg_fused<T, 0, false>) ? 0 : filt.F, pipe ? 1 : 0,
+                       sizeof(T), dim3((unsigned)grid), dim3(nt), lds3);
         hipLaunchKernelGGL(ki, dim3((unsigned)grid), dim3(nt), lds3, st, xw, x, (int)n, batch, L, filt, wx_sdwt_window_min_for(filt.F));
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
@@ -1574,6 +1589,7 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
         WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(ki), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
         int64_t grid = 256;
         if (grid > batch) grid = batch;
+        WX_SWT1D_TRACE(WX_RT_ISDIP, L, L, 0, 0, sizeof(T), dim3((unsigned)grid), dim3(1024), lds1);
         hipLaunchKernelGGL(ki, dim3((unsigned)grid), dim3(1024), lds1, st, xw, x, (int)n, batch, L, filt);
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;
@@ -1670,6 +1686,7 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
             if (gy > 65535) gy = 65535;
             const T *srcp = prev ? prev : xw;
             const int64_t src_cols = prev ? prev_cols : ncols;
+            WX_SWT1D_TRACE(WX_RT_IM, plan.from[i], K, R, OPT, sizeof(T), dim3((unsigned)(nodes_d * (((int64_t)1 << d) / R)), (unsigned)gy), dim3(NT), lds);
             hipLaunchKernelGGL(km, dim3((unsigned)(nodes_d * (((int64_t)1 << d) / R)), (unsigned)gy), dim3(NT), lds, st,
                                srcp, src_cols, outp, out_cols, (int)n, batch, d, R, (const double *)dcoef[slot],
                                dust, Utab[slot]);
@@ -1701,12 +1718,17 @@ int wx_dev_swt_inv(const T *xw, T *x, int64_t n, int L, int layout, int ncols, i
                 if (kt) {
                     if (ldst > 64 * 1024)
                         WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kt), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldst));
+                    WX_SWT1D_TRACE(WX_RT_ITILE, plan.from[i], 1, filt.F / 2, 0, sizeof(T), dim3((unsigned)gt), dim3(256), ldst);
                     hipLaunchKernelGGL(kt, dim3((unsigned)gt), dim3(256), ldst, st, D, (int)n, batch, Ptile, (int)halo, filt);
-                } else
+                } else {
+                    WX_SWT1D_TRACE(WX_RT_ILVL, plan.from[i], 1, 0, sm_mode, sizeof(T), dim3(wx_grid1(total)), dim3(256), 0);
                     hipLaunchKernelGGL(k_swt_inv_level<T>, dim3(wx_grid1(total)), dim3(256), 0, st, D, (int)n, batch, sm_mode, 0, 0, filt);
-            } else
-            hipLaunchKernelGGL(k_swt_inv_level<T>, dim3(wx_grid1(total)), dim3(256), 0, st, D, (int)n, batch, sm_mode,
-                               sm >= 0 ? (int)sd[d] : 0, sm >= 0 ? (int)sd[d + 1] : 0, filt);
+                }
+            } else {
+                WX_SWT1D_TRACE(WX_RT_ILVL, plan.from[i], 1, 0, sm_mode, sizeof(T), dim3(wx_grid1(total)), dim3(256), 0);
+                hipLaunchKernelGGL(k_swt_inv_level<T>, dim3(wx_grid1(total)), dim3(256), 0, st, D, (int)n, batch, sm_mode,
+                                   sm >= 0 ? (int)sd[d] : 0, sm >= 0 ? (int)sd[d + 1] : 0, filt);
+            }
         }
         prev = plan.buf[i] < 0 ? nullptr : outp;
         prev_cols = out_cols;
@@ -1719,6 +1741,7 @@ template <typename T>
 int wx_dev_iacdwt(const T *xw, T *x, int64_t n, int L, int64_t batch, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_SWT1D_TRACE(WX_RT_IACDWT, L, L, 0, 0, sizeof(T), dim3(wx_grid1(batch * n)), dim3(256), 0);
     hipLaunchKernelGGL(k_iacdwt<T>, dim3(wx_grid1(batch * n)), dim3(256), 0, st, xw, x, (int)n, L, batch);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
@@ -1727,6 +1750,7 @@ template <typename T>
 int wx_dev_iacwpt(const T *xw, T *x, int64_t n, int L, int64_t batch, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_SWT1D_TRACE(WX_RT_IACWPT, L, L, 0, 0, sizeof(T), dim3(wx_grid1(batch * n)), dim3(256), 0);
     hipLaunchKernelGGL(k_iacwpt<T>, dim3(wx_grid1(batch * n)), dim3(256), 0, st, xw, x, (int)n, L, batch);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
@@ -1736,10 +1760,67 @@ int wx_dev_iacwpd(const T *xw, T *x, int64_t n, int ncols, int64_t batch, const 
                   int Lfull, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_SWT1D_TRACE(WX_RT_IACWPD, Lfull, Lfull, 0, 0, sizeof(T), dim3(wx_grid1(batch * n)), dim3(256), 0);
     hipLaunchKernelGGL(k_iacwpd<T>, dim3(wx_grid1(batch * n)), dim3(256), 0, st, xw, x, (int)n, ncols, batch, dtree,
                        ntree, Lfull);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// launch record and schedule query of the parity suite (wx_debug.h; rows appended by WX_SWT1D_TRACE, wx_swt1d_trace.h)
+// ------------------------------------------------------------------------------------------
+std::atomic<int> wx_swt1d_trace_armed{0};
+static std::mutex g_swt1d_trace_mu;                      // test_gpu_stress.py calls the library from several threads
+static std::vector<int32_t> g_swt1d_trace_rows;
+static int64_t g_swt1d_trace_dropped = 0;
+
+void wx_swt1d_trace_add(int route, int depth, int K, int R, int OPT, size_t esz, dim3 grid, dim3 block, size_t lds)
+{
+    std::lock_guard<std::mutex> lk(g_swt1d_trace_mu);
+    if (!wx_swt1d_trace_armed.load(std::memory_order_relaxed)) return;
+    if (g_swt1d_trace_rows.size() >= (size_t)WX_SWT1D_TRACE_MAX * WX_SWT1D_TRACE_FIELDS) { ++g_swt1d_trace_dropped; return; }
+    const int32_t row[WX_SWT1D_TRACE_FIELDS] = {route, depth, K, R, OPT, (int32_t)esz, (int32_t)block.x, (int32_t)grid.x, (int32_t)grid.y,
+                                                (int32_t)grid.z, (int32_t)lds};
+    g_swt1d_trace_rows.insert(g_swt1d_trace_rows.end(), row, row + WX_SWT1D_TRACE_FIELDS);
+}
+
+extern "C" void wx_debug_swt1d_trace_begin(void)
+{
+    std::lock_guard<std::mutex> lk(g_swt1d_trace_mu);
+    g_swt1d_trace_rows.clear();
+    g_swt1d_trace_dropped = 0;
+    wx_swt1d_trace_armed.store(1);
+}
+
+extern "C" int wx_debug_swt1d_trace_end(int32_t *out, int cap)
+{
+    std::lock_guard<std::mutex> lk(g_swt1d_trace_mu);
+    if (!out || cap <= 0) return wx_set_error(WX_EARG, "wx_debug_swt1d_trace_end: no room for a single entry");
+    if (!wx_swt1d_trace_armed.load()) return wx_set_error(WX_EARG, "wx_debug_swt1d_trace_end without wx_debug_swt1d_trace_begin");
+    wx_swt1d_trace_armed.store(0);
+    const size_t rows = g_swt1d_trace_rows.size() / WX_SWT1D_TRACE_FIELDS;
+    const size_t ncopy = rows < (size_t)cap ? rows : (size_t)cap;
+    for (size_t i = 0; i < ncopy * WX_SWT1D_TRACE_FIELDS; ++i) out[i] = g_swt1d_trace_rows[i];
+    std::vector<int32_t>().swap(g_swt1d_trace_rows);
+    return (int)rows;
+}
+
+extern "C" int64_t wx_debug_swt1d_trace_dropped(void)
+{
+    std::lock_guard<std::mutex> lk(g_swt1d_trace_mu);
+    return g_swt1d_trace_dropped;
+}
+
+extern "C" int wx_debug_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, int elem_size, int has_tree, int haar6, int32_t *out)
+{
+    if (!out || n < 1 || L < 0 || L > 24 || F < 2 || layout < WX_LAYOUT_DWT || layout > WX_LAYOUT_WPD || (elem_size != 8 && elem_size != 4) ||
+        (layout == WX_LAYOUT_WPT && (n >> L) < 1))
+        return wx_set_error(WX_EARG, "wx_debug_swt_inv_plan: arguments outside the inverse transforms' domain");
+    WxSwtInvPlan P;
+    wx_swt_inv_plan(layout, L, F, sm, n, (size_t)elem_size, has_tree != 0, &P, haar6 != 0);
+    for (int i = 0; i < P.npass; ++i) { out[4 * i] = P.from[i]; out[4 * i + 1] = P.to[i]; out[4 * i + 2] = P.R[i]; out[4 * i + 3] = P.OPT[i]; }
+    return P.npass;
 }
 
 #define WX_INST(T)                                                                                              \

@@ -1,5 +1,6 @@
 // wx_swtdeep.hip -- launchers of the lane-local deep levels of swpt / acwpt (device code and the design notes: wx_swtdeep.h)
 #include "wx_swtdeep.h"
+#include "wx_swt1d_trace.h"
 
 // number of levels the lane-local kernel takes off the end of a depth-L swpt / acwpt of n-sample Float64 signals (0 = none)
 int wx_swpt_deep_levels(int64_t n, int L, int F, bool ac, size_t esz)
@@ -33,6 +34,7 @@ int wx_swpt_deep_fwd(double *xw, int64_t n, int L, int64_t batch, const WxFilt &
     if (isac) acz = *ac; else { acz.F = 0; acz.c1 = 0; }
     const int64_t gx = ((int64_t)1 << D0) * ((int64_t)1 << (D0 - 6));
     int64_t gy = batch > 65535 ? 65535 : batch;
+    WX_SWT1D_TRACE(WX_RT_FDEEP, D0, LP, 0, isac ? 1 : 0, sizeof(double), dim3((unsigned)gx, (unsigned)gy), dim3(64), 0);
     hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)gy), dim3(64), 0, st, xw, log2n, L, batch, filt, acz);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;

@@ -1,5 +1,6 @@
 // wx_swtdeep_i.hip -- launcher of the lane-local deep levels of the average-based iswpt (device code: wx_swtdeep.h)
 #include "wx_swtdeep.h"
+#include "wx_swt1d_trace.h"
 
 // the deepest LP = L - (log2(n) - 4) levels of the average-based iswpt: leaves (n, src_cols) -> nodes of depth L - LP (n, dst_cols)
 int wx_swpt_deep_inv(const double *src, int64_t src_cols, double *dst, int64_t dst_cols, int64_t n, int L, int LP, int64_t batch,
@@ -16,6 +17,7 @@ int wx_swpt_deep_inv(const double *src, int64_t src_cols, double *dst, int64_t d
     if (!k) return wx_set_error(WX_EHIP, "iswpt deep levels: no instantiation for this filter length");
     const int64_t gx = ((int64_t)1 << D0) * ((int64_t)1 << (D0 - 6));
     const int64_t gy = batch > 65535 ? 65535 : batch;
+    WX_SWT1D_TRACE(WX_RT_IDEEP, L, LP, 0, 0, sizeof(double), dim3((unsigned)gx, (unsigned)gy), dim3(64), 0);
     hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)gy), dim3(64), 0, st, src, src_cols, dst, dst_cols, log2n, batch, filt);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;

@@ -1,5 +1,6 @@
 // wx_swtdeep_w.hip -- launcher of the lane-local deep levels of swpd / acwpd (heap tables; device code: wx_swtdeep.h)
 #include "wx_swtdeep.h"
+#include "wx_swt1d_trace.h"
 
 int wx_swpd_deep_fwd_impl(double *xw, int64_t n, int L, int64_t batch, const WxFilt &filt, const WxAcFilt *ac, hipStream_t st)
 {
@@ -18,6 +19,7 @@ int wx_swpd_deep_fwd_impl(double *xw, int64_t n, int L, int64_t batch, const WxF
     if (isac) acz = *ac; else { acz.F = 0; acz.c1 = 0; }
     const int64_t gx = ((int64_t)1 << D0) * ((int64_t)1 << (D0 - 6));
     int64_t gy = batch > 65535 ? 65535 : batch;
+    WX_SWT1D_TRACE(WX_RT_FDEEP, D0, LP, 1, isac ? 1 : 0, sizeof(double), dim3((unsigned)gx, (unsigned)gy), dim3(64), 0);
     hipLaunchKernelGGL(k, dim3((unsigned)gx, (unsigned)gy), dim3(64), 0, st, xw, log2n, L, batch, filt, acz);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
