@@ -261,6 +261,32 @@ int wx_getbasiscoef2d_trees_f64(const double *Xw, double *out, int64_t m, int64_
 int wx_getbasiscoef2d_trees_f32(const float *Xw, float *out, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree,
                                 int64_t batch, void *stream);
 
+/* wptall / iwptall / iwpdall with ONE tree per signal, 1-D: the loops of dwt/dwt_all.jl:152-166 (wpt!), :210-225 (iwpt!) and
+ * :324-342 (iwpd!, DWT.jl:340-351) with the tree of signal b in column b of `trees` instead of one tree for the batch -- the
+ * BitMatrix convention of getbasiscoefall (Utils.jl:199-225), what bestbasistreeall (BestBasis.jl:253-262) returns.
+ * x, y, xhat: (n, batch); iwpd: xw (n, k, batch).  trees: HOST pointer, (ntree, batch) bytes, exactly as wx_getbasiscoef1d_trees_*;
+ * the matrix may be released on return (the call waits for its stream).  Data pointers may be host or device.
+ * Checked before anything is launched or written, and before a device is needed: n dyadic (WX_EASSERT), ntree == n - 1
+ * (WX_EASSERT), every column a valid tree (WX_EASSERT, :209); iwpd: every tree's depth < k (WX_EARG, Utils.jl:120); NULL trees with
+ * batch > 0 WX_EARG; batch == 0 is WX_OK.  In-place calls are NOT supported: x == y (xw == xhat) returns WX_EARG.
+ * Dyadic 8 <= n <= 8192 (Float64) / 16384 (Float32) with an even filter of 2 .. 20 taps: one launch, a workgroup per signal with
+ * the signal and its tree in LDS (csrc/wx_wpt_trees.hip).  Anything else (longer signals, other filter lengths, n < 8) is computed
+ * by the single-tree entry called once per signal inside the library: correct and slow.  Byte-identical columns are handed to the
+ * single-tree entry whole.  The leaves of wx_wpt1d_trees_* sit at their nodes' own ranges, i.e. y equals
+ * wx_getbasiscoef1d_trees_* of the wx_wpd1d_* table up to rounding. */
+int wx_wpt1d_trees_f64(const double *x, double *y, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
+                       int F, void *stream);
+int wx_wpt1d_trees_f32(const float *x, float *y, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
+                       int F, void *stream);
+int wx_iwpt1d_trees_f64(const double *xw, double *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+int wx_iwpt1d_trees_f32(const float *xw, float *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+int wx_iwpd1d_trees_f64(const double *xw, double *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+int wx_iwpd1d_trees_f32(const float *xw, float *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Standard (per-signal) best basis, BB -- SURVEY 8(f) row 3, widened after the 8(a) rows.

@@ -55,6 +55,31 @@ def _wpt_batched(name, x, y, sig_ndim, wt, L, tree):
         _call(name + "2d", x.suffix, x.ptr, y.ptr, m, n, L, tp, nt, B, qp, F, x.stream())
 
 
+def _trees_arg(trees, B):
+    """one tree per signal, (n-1, B) booleans (what bestbasistreeall(X, BB()) returns) -> (uint8 buffer kept alive, pointer, rows)"""
+    import ctypes
+    assert B == trees.shape[1]                                        # Utils.jl:210, the BitMatrix convention of getbasiscoefall
+    tb = np.asfortranarray(trees)                                     # column i = the tree of signal i
+    tb = tb.view(np.uint8) if tb.dtype == np.bool_ else tb.astype(np.uint8)   # booleans are bytes of 0 / 1 already: no copy
+    return tb, ctypes.c_void_p(tb.ctypes.data), int(tb.shape[0])
+
+
+def _wpt_trees(name, x, y, wt, trees):
+    """wptall / iwptall with one tree per signal (1-D): csrc/wx_wpt_trees.hip"""
+    q, qp, F = qmf_arg(wt)
+    n, B = x.shape[0], int(np.prod(x.shape[1:], dtype=np.int64))
+    tb, tp, nt = _trees_arg(trees, B)
+    _call(name + "1d_trees", x.suffix, x.ptr, y.ptr, n, tp, nt, B, qp, F, x.stream())
+
+
+def _iwpd_trees(xw, xh, wt, trees):
+    q, qp, F = qmf_arg(wt)
+    n, k = xw.shape[0], xw.shape[1]
+    B = int(np.prod(xw.shape[2:], dtype=np.int64))
+    tb, tp, nt = _trees_arg(trees, B)
+    _call("wx_iwpd1d_trees", xw.suffix, xw.ptr, xh.ptr, n, k, tp, nt, B, qp, F, xw.stream())
+
+
 def _iwpd_batched(xw, xh, sig_ndim, wt, L, tree):
     q, qp, F = qmf_arg(wt)
     tk, tp, nt = tree_arg(tree)
@@ -130,12 +155,16 @@ def iwpd_(xh, xw, wt, L_or_tree=None):
 
 
 def iwpdall(xw, wt, L_or_tree=None):
-    """dwt/dwt_all.jl:324-342: iwpd!(x̂ᵢ, xwᵢ, args...) over the last dimension."""
+    """dwt/dwt_all.jl:324-342: iwpd!(x̂ᵢ, xwᵢ, args...) over the last dimension.  1-D signals also take one tree per signal, a
+    boolean (n-1, N) matrix in place of `L | tree` (the BitMatrix convention of getbasiscoefall, Utils.jl:199-225)."""
     xw = Arg(xw)
     assert xw.arr.ndim > 2
     sz, N = xw.shape[:-2], xw.shape[-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     xh = xw.new(sz + (N,))
+    if tree is not None and tree.ndim == 2 and len(sz) == 1:
+        _iwpd_trees(xw, xh, wt, tree)
+        return xh.arr
     _iwpd_batched(xw, xh, len(sz), wt, L, tree)
     return xh.arr
 
@@ -178,17 +207,21 @@ def _wptall_like(name, x, wt, L_or_tree):
     sz = x.shape[:-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     y = x.new(x.shape)
+    if tree is not None and tree.ndim == 2 and len(sz) == 1:
+        _wpt_trees(name, x, y, wt, tree)
+        return y.arr
     _wpt_batched(name, x, y, len(sz), wt, L, tree)
     return y.arr
 
 
 def wptall(x, wt, L_or_tree=None):
-    """dwt/dwt_all.jl:152-166"""
+    """dwt/dwt_all.jl:152-166.  1-D signals also take one tree per signal, a boolean (n-1, N) matrix in place of `L | tree`:
+    the result is getbasiscoefall(wpdall(x, wt), trees) without the table."""
     return _wptall_like("wx_wpt", x, wt, L_or_tree)
 
 
 def iwptall(xw, wt, L_or_tree=None):
-    """dwt/dwt_all.jl:210-225"""
+    """dwt/dwt_all.jl:210-225.  1-D signals also take one tree per signal, as wptall."""
     return _wptall_like("wx_iwpt", xw, wt, L_or_tree)
 
 

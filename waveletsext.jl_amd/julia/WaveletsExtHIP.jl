@@ -110,6 +110,9 @@ c_getbasiscoef(T, Xw, out, sig::NTuple{2,Int}, k, tb, nt, N) = check(wx_getbasis
 c_getbasiscoef_trees(T, Xw, out, sig::NTuple{1,Int}, k, tb, nt, N) = check(wx_getbasiscoef1d_trees(T, Xw, out, sig[1], k, tb, nt, N, stream()))
 c_getbasiscoef_trees(T, Xw, out, sig::NTuple{2,Int}, k, tb, nt, N) =
     check(wx_getbasiscoef2d_trees(T, Xw, out, sig[1], sig[2], k, tb, nt, N, stream()))
+c_wpt_trees(T, x, y, n, tb, nt, N, q) = check(wx_wpt1d_trees(T, x, y, n, tb, nt, N, q, length(q), stream()))
+c_iwpt_trees(T, xw, x, n, tb, nt, N, q) = check(wx_iwpt1d_trees(T, xw, x, n, tb, nt, N, q, length(q), stream()))
+c_iwpd_trees(T, xw, x, n, k, tb, nt, N, q) = check(wx_iwpd1d_trees(T, xw, x, n, k, tb, nt, N, q, length(q), stream()))
 c_dwt3d(T, x, y, sig::NTuple{3,Int}, L, N, q) = check(wx_dwt3d(T, x, y, sig[1], sig[2], sig[3], L, N, q, length(q), stream()))
 c_idwt3d(T, x, y, sig::NTuple{3,Int}, L, N, q) = check(wx_idwt3d(T, x, y, sig[1], sig[2], sig[3], L, N, q, length(q), stream()))
 
@@ -334,6 +337,34 @@ function getbasiscoefall(Xw::HIP{T}, trees::BitMatrix) where T<:FT
     tb = Matrix{UInt8}(trees)
     c_getbasiscoef_trees(T, raw(Xw), out, sz, k, tb, size(tb, 1), N)
     return out
+end
+
+# the transforms with one tree per signal, 1-D (the loops of dwt/dwt_all.jl:152-166, 210-225, 324-342 with column i of `trees` for
+# signal i -- the BitMatrix convention of getbasiscoefall above): wptall(x, wt, trees) is getbasiscoefall(wpdall(x, wt), trees)
+# without the table, and iwptall / iwpdall rebuild every signal from its own basis, one launch each (csrc/wx_wpt_trees.hip)
+function wptall(x::HIP{T,2}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    n, N = size(x)
+    @assert size(trees, 2) == N
+    y = newlike(x, T, size(x))
+    tb = Matrix{UInt8}(trees)
+    c_wpt_trees(T, raw(x), y, n, tb, size(tb, 1), N, qmfvec(wt))
+    return y
+end
+function iwptall(xw::HIP{T,2}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    n, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, size(xw))
+    tb = Matrix{UInt8}(trees)
+    c_iwpt_trees(T, raw(xw), x̂, n, tb, size(tb, 1), N, qmfvec(wt))
+    return x̂
+end
+function iwpdall(xw::HIP{T,3}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, (n, N))
+    tb = Matrix{UInt8}(trees)
+    c_iwpd_trees(T, raw(xw), x̂, n, k, tb, size(tb, 1), N, qmfvec(wt))
+    return x̂
 end
 
 # ---------------------------------------------------------------------------------------------------------------------
