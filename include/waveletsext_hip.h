@@ -249,8 +249,10 @@ int wx_getbasiscoef2d_f64(const double *Xw, double *out, int64_t m, int64_t n, i
 int wx_getbasiscoef2d_f32(const float *Xw, float *out, int64_t m, int64_t n, int k, const uint8_t *tree, int64_t ntree,
                           int64_t batch, void *stream);
 /* getbasiscoefall(Xw, tree::BitArray{2}) Utils.jl:199-225: ONE tree per signal -- what bestbasistreeall (BestBasis.jl:253-262)
- * returns.  trees: HOST pointer, (ntree, batch) bytes, column b = the tree of signal b (a Julia BitMatrix converted with
- * Matrix{UInt8}); every tree is checked like the reference does (:209), one launch gathers all signals.
+ * returns.  trees: host OR device pointer (see "Per-signal tree matrices" below), (ntree, batch) bytes, column b = the tree of
+ * signal b (a Julia BitMatrix converted with Matrix{UInt8}, or what wx_treeselect_batch_* wrote); every tree is checked like the
+ * reference does (:209), one launch gathers all signals.  A device matrix is checked by one launch and read by the gather where it
+ * is: no staging copy.
  * 1-D: Xw (n, k, batch) -> out (n, batch); 2-D: Xw (m, n, k, batch) -> out (m, n, batch). */
 int wx_getbasiscoef1d_trees_f64(const double *Xw, double *out, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                                 void *stream);
@@ -264,8 +266,8 @@ int wx_getbasiscoef2d_trees_f32(const float *Xw, float *out, int64_t m, int64_t 
 /* wptall / iwptall / iwpdall with ONE tree per signal, 1-D: the loops of dwt/dwt_all.jl:152-166 (wpt!), :210-225 (iwpt!) and
  * :324-342 (iwpd!, DWT.jl:340-351) with the tree of signal b in column b of `trees` instead of one tree for the batch -- the
  * BitMatrix convention of getbasiscoefall (Utils.jl:199-225), what bestbasistreeall (BestBasis.jl:253-262) returns.
- * x, y, xhat: (n, batch); iwpd: xw (n, k, batch).  trees: HOST pointer, (ntree, batch) bytes, exactly as wx_getbasiscoef1d_trees_*;
- * the matrix may be released on return (the call waits for its stream).  Data pointers may be host or device.
+ * x, y, xhat: (n, batch); iwpd: xw (n, k, batch).  trees: host or device pointer, (ntree, batch) bytes, exactly as
+ * wx_getbasiscoef1d_trees_*; a HOST matrix may be released on return (the call waits for its stream).  Data pointers may be host or device.
  * Checked before anything is launched or written, and before a device is needed: n dyadic (WX_EASSERT), ntree == n - 1
  * (WX_EASSERT), every column a valid tree (WX_EASSERT, :209); iwpd: every tree's depth < k (WX_EARG, Utils.jl:120); NULL trees with
  * batch > 0 WX_EARG; batch == 0 is WX_OK.  In-place calls are NOT supported: x == y (xw == xhat) returns WX_EARG.
@@ -286,6 +288,26 @@ int wx_iwpd1d_trees_f64(const double *xw, double *xhat, int64_t n, int k, const 
                         const double *qmf, int F, void *stream);
 int wx_iwpd1d_trees_f32(const float *xw, float *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream);
+
+/* Per-signal tree matrices: `trees` of the ten wx_*_trees_* entries above is host or device memory, told apart like the data
+ * pointers (hipPointerGetAttributes); any non-zero byte means "decomposed".  A host matrix is handled as before.  A DEVICE matrix
+ * -- the output of wx_treeselect_batch_* on device costs, never copied back -- follows these rules:
+ *  - it must live on the current device, else WX_EARG; the argument checks that need no tree content (dimensions, NULL, aliasing,
+ *    dyadic, ntree) come first, with the order and codes of the host route;
+ *  - one launch (csrc/wx_trees_prep.hip) checks every column (valid tree: WX_EASSERT; depth < k where the entry has a k: WX_EARG;
+ *    the lowest offending column decides, as on the host), and the call waits for its stream ONCE, to read that launch's status
+ *    record; errors from the tree content are reported before any output element is written;
+ *  - wx_wpt1d_trees_* / wx_iwpt1d_trees_* / wx_iwpd1d_trees_* inside the LDS kernel's window (above): the same launch packs the
+ *    trees into the kernel's bit layout and notes their depths; the matrix never reaches the host, and with device data the call
+ *    returns with the transform queued.  All columns equal byte for byte: column 0 (ntree bytes) goes to the host and the
+ *    single-tree entry runs, so the result is the host route's.  Outside the window the matrix is copied to the host once and
+ *    the host route runs: correct and slow;
+ *  - wx_getbasiscoef1d_trees_* / wx_getbasiscoef2d_trees_*: the gather reads the caller's matrix; with device data the call returns
+ *    with the gather queued, so the matrix must stay valid until the stream has passed it.
+ * wx_wpt_trees_last_route: the way the last of these ten calls went on the calling thread: 0 = none yet, or that call returned an
+ * error; 1 = host trees; 2 = device trees, prep launch + LDS kernel; 3 = device trees, prep launch + single-tree entry;
+ * 4 = device trees copied to the host (outside the window); 5 = device trees, prep launch + gather. */
+int wx_wpt_trees_last_route(void);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -152,6 +152,28 @@ def tree_arg(tree):
     return t, ctypes.c_void_p(t.ctypes.data), int(t.size)
 
 
+def trees_arg(trees, B, data):
+    """one tree per signal, (tree length, B) booleans or bytes (what bestbasistreeall(X, BB()) returns) -> (buffer kept alive, pointer,
+    rows).  A numpy matrix goes over as a host pointer; a device tensor of torch.bool / torch.uint8 (bestbasistreeall(..., device=True))
+    as its device pointer, made column-major on the device if it is not: then `data`, the call's data argument, must be a tensor
+    on the same device, and the call is queued on torch's current stream like every call with device data."""
+    if is_torch(trees) and trees.device.type != "cpu":
+        if trees.dtype not in (torch.bool, torch.uint8) or trees.dim() != 2:
+            raise TypeError("a device tree matrix must be a 2-D tensor of torch.bool or torch.uint8")
+        if data.kind != "torch" or data.device != trees.device:
+            raise TypeError("device trees need the data on the same device")
+        assert B == trees.shape[1]                                    # Utils.jl:210
+        tb = to_colmajor(trees)                                       # column i = the tree of signal i
+        return tb, ctypes.c_void_p(tb.data_ptr()), int(tb.shape[0])
+    if is_torch(trees):
+        trees = trees.numpy()
+    trees = np.asarray(trees)
+    assert B == trees.shape[1]                                        # Utils.jl:210, the BitMatrix convention of getbasiscoefall
+    tb = np.asfortranarray(trees)                                     # column i = the tree of signal i
+    tb = tb.view(np.uint8) if tb.dtype == np.bool_ else tb.astype(np.uint8)   # booleans are bytes of 0 / 1 already: no copy
+    return tb, ctypes.c_void_p(tb.ctypes.data), int(tb.shape[0])
+
+
 def qmf_arg(wt):
     q = np.ascontiguousarray(np.asarray(wt.qmf, dtype=np.float64))
     return q, ctypes.c_void_p(q.ctypes.data), int(q.size)

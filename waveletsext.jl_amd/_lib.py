@@ -144,6 +144,7 @@ _PLAIN_SIGS = {
     "wx_treeselect2d_f64": [_P, _L, _L, _L, _I, _P],
     "wx_treeselect2d_f32": [_P, _L, _L, _L, _I, _P],
     "wx_shutdown": [],
+    "wx_wpt_trees_last_route": [],
     "wx_set_host_hugepages": [_I],
     "wx_energy_map_f64": [_P, _L, _L, _L, _P, _I, _P, _P, _P],
     "wx_energy_map_f32": [_P, _L, _L, _L, _P, _I, _P, _P, _P],
@@ -267,6 +268,17 @@ def red2d_route(inverse, m, n, L, elem_size, F, ac=False, shift=False):
     if code < 0:
         raise ValueError("wx_debug_red2d_route: arguments outside the transforms' domain")
     return RED2D_ROUTES[code & 255], code >> 8
+
+
+# include/waveletsext_hip.h: wx_wpt_trees_last_route
+WPT_TREES_ROUTES = {0: "none", 1: "host trees", 2: "device prep + lds kernel", 3: "device prep + single tree",
+                    4: "device trees copied to host", 5: "device prep + gather"}
+
+
+def wpt_trees_route():
+    """which way the last wptall / iwptall / iwpdall / getbasiscoefall call with one tree per signal went on this thread
+    (wx_wpt_trees_last_route): one of WPT_TREES_ROUTES' strings; "none" before the first such call and after one that raised"""
+    return WPT_TREES_ROUTES[lib().wx_wpt_trees_last_route()]
 
 
 # csrc/wx_debug.h: route ids of the 1-D redundant transforms' launch record

@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._arrays import Arg, qmf_arg, to_numpy
+from ._arrays import Arg, is_torch, qmf_arg, to_numpy
 from .dwt import _call
 from .filters import ArgumentError
 from .util import gettreelength, maxtransformlevels
@@ -168,17 +168,24 @@ def _bb_trees(costs, sig, N, kind="min"):
     return trees
 
 
-def bestbasistreeall(X, method=None):
+def bestbasistreeall(X, method=None, device=False):
     """bestbasistreeall(X, BB(...)) BestBasis.jl:253-262: X (n, k, N) or (n, m, k, N) -> BitMatrix (tree length, N);
-    costs and the selection of all N trees run on the device."""
+    costs and the selection of all N trees run on the device.  device=True (X a device tensor): the selection's output itself, a
+    column-major (tree length, N) torch.bool view on X's device -- no copy, no synchronisation; wptall / iwptall / iwpdall /
+    getbasiscoefall take it as it is."""
     method = BB() if method is None else method
     if not isinstance(method, BB):
         raise TypeError("bestbasistreeall takes a BB method (BestBasis.jl:253)")
+    if device and not (is_torch(X) and X.device.type != "cpu"):
+        raise TypeError("bestbasistreeall(..., device=True) takes a device tensor")
     Xa = Arg(X)
     assert 3 <= Xa.arr.ndim <= 4                                      # BestBasis.jl:254
     sig = Xa.shape[:-2]
     costs = _bb_costs(Xa, method, True)
     trees = _bb_trees(costs, sig, Xa.shape[-1])
+    if device:
+        import torch
+        return trees.T.view(torch.bool)                # (tree length, N) column-major; the selection writes bytes of 0 / 1
     if costs.kind == "torch":
         # device -> page-locked host memory (torch's caching host allocator) -> numpy view of it: .cpu() into pageable memory and a uint8 -> bool
         # copy were most of the call for short signals (19 MB of trees per GiB of table at 64 samples)

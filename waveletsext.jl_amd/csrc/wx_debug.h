@@ -69,6 +69,11 @@ int64_t wx_debug_swt1d_trace_dropped(void);
  * out receives from, to, R, OPT of every pass (4 * L values at most; OPT = 0 marks the Haar register pass, -1 the lane-local one);
  * returns the number of passes, or WX_EARG (-2) for n < 1, L outside 0..24 (wpt: 2^L > n), F < 2, another layout or element size. */
 int wx_debug_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, int elem_size, int has_tree, int haar6, int32_t *out);
+
+/* The bit layout the per-signal-tree kernel reads (csrc/wx_tree_bits.h), by the host routine that packs host tree matrices: tree =
+ * n - 1 bytes (any non-zero byte = decomposed), words receives max(n / 32, 1) words with the bits past node n - 1 zero.  Needs no
+ * device.  Returns the number of words, or WX_EARG (-2) for a NULL pointer or n < 2. */
+int wx_debug_pack_tree1d(const uint8_t *tree, int64_t n, uint32_t *words);
 #ifdef __cplusplus
 }
 #endif

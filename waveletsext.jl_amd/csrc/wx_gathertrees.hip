@@ -4,9 +4,12 @@
 // "missing" 3).  Here the (ntree, batch) byte matrix goes to the device once and one launch gathers every signal: a workgroup
 // takes a signal, keeps its tree in LDS and every thread walks from the root to the leaf that owns its position -- the depth of
 // that leaf is the column (slice) of the packet table the coefficient comes from.
+// A tree matrix that is in device memory already (bestbasistreeall's own output) is checked there by one launch (wx_trees_prep.hip)
+// and the gather reads the caller's matrix: no staging copy, no host pass.
 #include "../../include/waveletsext_hip.h"
 #include "wx_common.h"
 #include "wx_host.h"
+#include "wx_trees_prep.h"
 
 #define WX_REQUIRE(cond, code, msg) \
     do { if (!(cond)) return wx_set_error(code, msg); } while (0)
@@ -92,37 +95,50 @@ int gt_need_device()
     return WX_OK;
 }
 
+// the checks of a host matrix's columns below, for a matrix in device memory: one launch, the codes and the first-offending-column
+// rule are the same
+int gt_check_device_trees(bool quad, const uint8_t *trees, int64_t ntree, int64_t batch, int k, hipStream_t st)
+{
+    WX_REQUIRE(!wx_on_other_device(trees), WX_EARG, "tree matrix lives on another device than the current one");
+    return wx_trees_prep(quad, trees, ntree, batch, k, nullptr, 0, nullptr, nullptr, nullptr, st);
+}
+
 // every tree is checked like the reference does (`@assert all(mapslices(isvalidtree, tree))`, Utils.jl:209) and must not reach below
 // the table (Utils.jl:120, raised by the per-signal getbasiscoef)
 template <typename T>
 int api_trees1d(const T *Xw, T *out, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
 {
+    wx_trees_route_set(WX_TREES_ROUTE_NONE);
     WX_REQUIRE(n >= 1 && batch >= 0 && k >= 1, WX_EARG, "getbasiscoefall: bad dimensions");
     WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
     WX_REQUIRE(wx_isdyadic(n), WX_EASSERT, "@assert leaf_len == length(leaf) (Utils.jl:113)");
     WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
     WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
     WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "getbasiscoefall: signal length >= 2^30 not supported");
-    for (int64_t b = 0; b < batch; ++b) {
-        const uint8_t *t = trees + b * ntree;
-        WX_REQUIRE(wx_isvalidtree1d(n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-        WX_REQUIRE(wx_tree_depth1d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
-    }
+    const bool dev_trees = batch > 0 && wx_is_device_ptr(trees);
+    hipStream_t st = wx_stream(stream);
     int rc;
+    if (dev_trees) {
+        if ((rc = gt_check_device_trees(false, trees, ntree, batch, k, st))) return rc;
+    } else
+        for (int64_t b = 0; b < batch; ++b) {
+            const uint8_t *t = trees + b * ntree;
+            WX_REQUIRE(wx_isvalidtree1d(n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
+            WX_REQUIRE(wx_tree_depth1d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
+        }
     if ((rc = gt_need_device())) return rc;
     if (batch == 0) return WX_OK;
-    hipStream_t st = wx_stream(stream);
     WxScratch scr(st);
-    uint8_t *dt = (uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch);
-    if (!dt) return WX_EHIP;
+    const uint8_t *dt = trees;                                         // device trees are read where they are
+    if (!dev_trees && !(dt = (const uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch))) return WX_EHIP;
     WxIO io(st);
     const T *dX = (const T *)io.in(Xw, sizeof(T) * n * k * batch);
     T *dout = (T *)io.out(out, sizeof(T) * n * batch);
     if (!dX || !dout) return io.finish(WX_EHIP);
     // the tree matrix goes over from the caller's (pageable) memory: every return behind this copy waits for the stream first, so the
     // matrix may be released on return whatever the outcome
-    if (ntree > 0) {
-        hipError_t e = hipMemcpyAsync(dt, trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
+    if (ntree > 0 && !dev_trees) {
+        hipError_t e = hipMemcpyAsync(const_cast<uint8_t *>(dt), trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(st);
             return io.finish(wx_set_hip_error(e, "getbasiscoefall: tree upload", __FILE__, __LINE__));
@@ -131,48 +147,55 @@ int api_trees1d(const T *Xw, T *out, int64_t n, int k, const uint8_t *trees, int
     const unsigned grid = (unsigned)(batch < 65536 * 4 ? batch : 65536 * 4);
     if (ntree <= GT_LDS_MAX)
         hipLaunchKernelGGL((k_gather_trees1d<T, true>), dim3(grid), dim3(256), (size_t)ntree + 16, st, dX, dout, (int)n, gt_log2(n), k, batch,
-                           (const uint8_t *)dt, (int)ntree);
+                           dt, (int)ntree);
     else
         hipLaunchKernelGGL((k_gather_trees1d<T, false>), dim3(grid), dim3(256), 0, st, dX, dout, (int)n, gt_log2(n), k, batch,
-                           (const uint8_t *)dt, (int)ntree);
+                           dt, (int)ntree);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                 // the host tree matrix may be released on return
+    if (e == hipSuccess && !dev_trees) e = hipStreamSynchronize(st);   // the host tree matrix may be released on return
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return io.finish(wx_set_hip_error(e, "getbasiscoefall launch", __FILE__, __LINE__));
     }
-    return io.finish(WX_OK);
+    rc = io.finish(WX_OK);
+    if (rc == WX_OK) wx_trees_route_set(dev_trees ? WX_TREES_ROUTE_DEV_GATHER : WX_TREES_ROUTE_HOST);
+    return rc;
 }
 
 template <typename T>
 int api_trees2d(const T *Xw, T *out, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
 {
+    wx_trees_route_set(WX_TREES_ROUTE_NONE);
     WX_REQUIRE(m >= 1 && n >= 1 && batch >= 0 && k >= 1, WX_EARG, "getbasiscoefall: bad dimensions");
     WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
     const int Lmax = wx_maxtransformlevels(m < n ? m : n);
     WX_REQUIRE(k - 1 <= Lmax, WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
     WX_REQUIRE(ntree == wx_gettreelength2d(m, n), WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
     WX_REQUIRE(m < ((int64_t)1 << 20) && n < ((int64_t)1 << 20) && ntree < ((int64_t)1 << 31), WX_EUNSUPPORTED, "getbasiscoefall: image side >= 2^20");
-    for (int64_t b = 0; b < batch; ++b) {
-        const uint8_t *t = trees + b * ntree;
-        WX_REQUIRE(wx_isvalidtree2d(m, n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-        WX_REQUIRE(wx_tree_depth2d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
-    }
+    const bool dev_trees = batch > 0 && wx_is_device_ptr(trees);
+    hipStream_t st = wx_stream(stream);
     int rc;
+    if (dev_trees) {
+        if ((rc = gt_check_device_trees(true, trees, ntree, batch, k, st))) return rc;
+    } else
+        for (int64_t b = 0; b < batch; ++b) {
+            const uint8_t *t = trees + b * ntree;
+            WX_REQUIRE(wx_isvalidtree2d(m, n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
+            WX_REQUIRE(wx_tree_depth2d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
+        }
     if ((rc = gt_need_device())) return rc;
     if (batch == 0) return WX_OK;
-    hipStream_t st = wx_stream(stream);
     WxScratch scr(st);
-    uint8_t *dt = (uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch);
-    if (!dt) return WX_EHIP;
+    const uint8_t *dt = trees;                                         // device trees are read where they are
+    if (!dev_trees && !(dt = (const uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch))) return WX_EHIP;
     WxIO io(st);
     const T *dX = (const T *)io.in(Xw, sizeof(T) * m * n * k * batch);
     T *dout = (T *)io.out(out, sizeof(T) * m * n * batch);
     if (!dX || !dout) return io.finish(WX_EHIP);
     // the tree matrix goes over from the caller's (pageable) memory: every return behind this copy waits for the stream first, so the
     // matrix may be released on return whatever the outcome
-    if (ntree > 0) {
-        hipError_t e = hipMemcpyAsync(dt, trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
+    if (ntree > 0 && !dev_trees) {
+        hipError_t e = hipMemcpyAsync(const_cast<uint8_t *>(dt), trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
             (void)hipStreamSynchronize(st);
             return io.finish(wx_set_hip_error(e, "getbasiscoefall: tree upload", __FILE__, __LINE__));
@@ -181,17 +204,19 @@ int api_trees2d(const T *Xw, T *out, int64_t m, int64_t n, int k, const uint8_t 
     const unsigned grid = (unsigned)(batch < 65536 * 4 ? batch : 65536 * 4);
     if (ntree <= GT_LDS_MAX)
         hipLaunchKernelGGL((k_gather_trees2d<T, true>), dim3(grid), dim3(256), (size_t)ntree + 16, st, dX, dout, (int)m, (int)n, k, batch,
-                           (const uint8_t *)dt, (int)ntree);
+                           dt, (int)ntree);
     else
         hipLaunchKernelGGL((k_gather_trees2d<T, false>), dim3(grid), dim3(256), 0, st, dX, dout, (int)m, (int)n, k, batch,
-                           (const uint8_t *)dt, (int)ntree);
+                           dt, (int)ntree);
     hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && !dev_trees) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return io.finish(wx_set_hip_error(e, "getbasiscoefall launch", __FILE__, __LINE__));
     }
-    return io.finish(WX_OK);
+    rc = io.finish(WX_OK);
+    if (rc == WX_OK) wx_trees_route_set(dev_trees ? WX_TREES_ROUTE_DEV_GATHER : WX_TREES_ROUTE_HOST);
+    return rc;
 }
 
 }  // namespace

@@ -8,6 +8,8 @@ hipStream_t wx_stream(void *s);
 
 // true if p is device-accessible memory owned by HIP (device or managed allocation)
 bool wx_is_device_ptr(const void *p);
+// true if p is device memory of another device than the current one (the kernels are launched on the current one)
+bool wx_on_other_device(const void *p);
 
 int wx_pack_filter(const double *qmf, int F, WxFilt *out);
 

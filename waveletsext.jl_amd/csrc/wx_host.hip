@@ -36,7 +36,7 @@ bool wx_is_device_ptr(const void *p)
 
 // device memory must belong to the current device: the kernels are launched there (one process per GPU is the
 // intended deployment; a caller driving several GPUs from one process selects the device before each call)
-static bool wx_on_other_device(const void *p)
+bool wx_on_other_device(const void *p)
 {
     hipPointerAttribute_t a;
     memset(&a, 0, sizeof a);

@@ -16,7 +16,8 @@
 //   iwpd      the inverse kernel whose loads take every position from the column of its leaf's depth in the packet table
 //             (getbasiscoef, Utils.jl:101-134).
 // The host checks every tree (a few threads for a large matrix), notes its depth and packs it into bits in the same pass: the kernel
-// gets n / 8 bytes of tree per signal instead of n - 1.
+// gets n / 8 bytes of tree per signal instead of n - 1.  A tree matrix in DEVICE memory (bestbasistreeall's own output) gets the
+// same pass as one launch (wx_trees_prep.hip) and never visits the host inside the window.
 // The filter length is a loop bound: six kernels in all (3 directions x 2 types), the arithmetic is Float64 for either type like the
 // one-level kernels of wx_dwt1d.hip.  No atomics; every output element is written by exactly one lane.
 // Window: what wx_fused1d_ok admits (dyadic 8 <= n <= 8192 Float64 / 16384 Float32, even filters of 2 .. 20 taps).  Outside it the
@@ -25,6 +26,8 @@
 #include "wx_common.h"
 #include "wx_host.h"
 #include "wx_kernels.h"
+#include "wx_tree_bits.h"
+#include "wx_trees_prep.h"
 #include <cstring>
 #include <thread>
 #include <vector>
@@ -38,9 +41,7 @@ namespace {
 
 enum { WT_FWD = 0, WT_INV = 1, WT_IWPD = 2 };
 
-// the tree of a signal as bits: node i (1-based, heap order) is bit (i - 1) & 31 of word (i - 1) >> 5; n / 32 words (at least one)
-__host__ __device__ __forceinline__ int wt_words(int64_t n) { return n >= 32 ? (int)(n >> 5) : 1; }
-__device__ __forceinline__ bool wt_set(const uint32_t *tree, int node) { return (tree[(node - 1) >> 5] >> ((node - 1) & 31)) & 1u; }
+// the tree of a signal as bits: wt_words, wt_set (wx_tree_bits.h)
 
 // depth of the leaf that owns position p (binary heap: children 2i, 2i + 1; utils_tree.jl:57-75)
 __device__ __forceinline__ int wt_leaf_depth(const uint32_t *tree, int ntree, int p, int log2n)
@@ -189,10 +190,85 @@ int wt_single(const float *x, float *y, int64_t n, int k, const uint8_t *t, int6
     return wx_iwpd1d_f32(x, y, n, k, 0, t, nt, batch, qmf, F, st);
 }
 
+template <typename T> bool wt_lds_path(int64_t n, int F) { return wx_fused1d_ok<T>(n, F) && wt_lds_bytes<T>(n) <= 160 * 1024; }
+
+// the launch of k_wpt_trees: dt = the trees' bits, dd = one depth byte per signal, both in device memory
+template <typename T, int MODE>
+hipError_t wt_launch(const T *dx, T *dy, int64_t n, int k, int64_t batch, const uint32_t *dt, const uint8_t *dd, const WxFilt &filt,
+                     hipStream_t st)
+{
+    const size_t lds = wt_lds_bytes<T>(n);
+    const int nt = wt_threads(n);
+    auto kern = k_wpt_trees<T, MODE>;
+    hipError_t e = hipSuccess;
+    if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    int log2n = 0;
+    while (((int64_t)1 << log2n) < n) ++log2n;
+    hipLaunchKernelGGL(kern, dim3(wt_grid(lds, nt, batch)), dim3(nt), lds, st, dx, dy, log2n, k, batch, dt, dd, filt);
+    return hipGetLastError();
+}
+
+template <typename T, int MODE>
+int wt_host_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
+                  void *stream, const WxFilt &filt);
+
+// trees in device memory (batch > 0, the argument checks that need no tree content are done): see include/waveletsext_hip.h
+template <typename T, int MODE>
+int wt_device_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
+                    void *stream, const WxFilt &filt)
+{
+    WX_REQUIRE(!wx_on_other_device(trees), WX_EARG, "tree matrix lives on another device than the current one");
+    hipStream_t st = wx_stream(stream);
+    if (!wt_lds_path<T>(n, F)) {
+        // outside the LDS kernel's window: the matrix comes to the host once and the host path runs (correct and slow)
+        std::vector<uint8_t> ht((size_t)(ntree > 0 ? ntree * batch : 1));
+        if (ntree > 0) {
+            hipError_t e = hipMemcpyAsync(ht.data(), trees, (size_t)ntree * batch, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                (void)hipStreamSynchronize(st);
+                return wx_set_hip_error(e, "wptall(trees): tree matrix to the host", __FILE__, __LINE__);
+            }
+        }
+        const int rc = wt_host_trees<T, MODE>(x, y, n, k, ht.data(), ntree, batch, qmf, F, stream, filt);
+        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_COPIED);
+        return rc;
+    }
+    const int nw = wt_words(n);
+    WxScratch scr(st);
+    const size_t tbytes = sizeof(uint32_t) * nw * (size_t)batch;
+    uint8_t *dt = (uint8_t *)scr.alloc(tbytes + (size_t)batch);         // the trees' bits, then one depth byte per signal
+    if (!dt) return WX_EHIP;
+    uint8_t *dd = dt + tbytes;
+    std::vector<uint8_t> col0((size_t)ntree);
+    bool same = true;
+    int rc = wx_trees_prep(false, trees, ntree, batch, MODE == WT_IWPD ? k : 0, (uint32_t *)dt, nw, dd, col0.data(), &same, st);
+    if (rc) return rc;                                                 // nothing has been written to y
+    if (same) {                                                        // one tree after all: as the host path does, with the same result
+        rc = wt_single(x, y, n, k, col0.data(), ntree, batch, qmf, F, stream, MODE);
+        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_SINGLE);
+        return rc;
+    }
+    WxIO io(st);
+    const T *dx = (const T *)io.in(x, sizeof(T) * n * (MODE == WT_IWPD ? k : 1) * batch);
+    T *dy = (T *)io.out(y, sizeof(T) * n * batch);
+    if (!dx || !dy) return io.finish(WX_EHIP);
+    const hipError_t e = wt_launch<T, MODE>(dx, dy, n, k, batch, (const uint32_t *)dt, dd, filt, st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return io.finish(wx_set_hip_error(e, "wptall(trees) launch", __FILE__, __LINE__));
+    }
+    rc = io.finish(WX_OK);                                             // device arrays: nothing waits, the scratch is freed in stream order
+    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_LDS);
+    return rc;
+}
+
 template <typename T, int MODE>
 int api_wpt_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
                   void *stream)
 {
+    wx_trees_route_set(WX_TREES_ROUTE_NONE);
     WxFilt filt;
     int rc = wx_pack_filter(qmf, F, &filt);
     if (rc) return rc;
@@ -204,10 +280,22 @@ int api_wpt_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int6
     if (MODE == WT_IWPD) WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "getbasiscoef: @assert k-1 <= L (Utils.jl:110)");
     WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
     WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "wptall(trees): signal length >= 2^30 not supported");
+    if (batch > 0 && wx_is_device_ptr(trees)) return wt_device_trees<T, MODE>(x, y, n, k, trees, ntree, batch, qmf, F, stream, filt);
+    rc = wt_host_trees<T, MODE>(x, y, n, k, trees, ntree, batch, qmf, F, stream, filt);
+    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_HOST);
+    return rc;
+}
+
+// trees in host memory
+template <typename T, int MODE>
+int wt_host_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
+                  void *stream, const WxFilt &filt)
+{
+    int rc;
     // every tree is checked like the reference does (Utils.jl:209), and for iwpd must not reach below the table (Utils.jl:120); the
     // first offending column decides the error.  A large matrix is checked by a few host threads, a range of columns each.
     // The LDS kernel takes the trees as bits (an eighth of the bytes to upload), packed by the same pass.
-    const bool lds_path = wx_fused1d_ok<T>(n, F) && wt_lds_bytes<T>(n) <= 160 * 1024;
+    const bool lds_path = wt_lds_path<T>(n, F);
     const int nw = wt_words(n);
     std::vector<uint8_t> depths((size_t)(batch > 0 ? batch : 1));
     std::vector<uint32_t> bits(lds_path ? (size_t)nw * batch : 0);
@@ -224,18 +312,7 @@ int api_wpt_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int6
             }
             if (code) { out->code = code; return; }
             if (out->same && ntree > 0) out->same = memcmp(trees, t, (size_t)ntree) == 0;
-            if (lds_path) {
-                // eight nodes at a time: 0x80 where a byte is non-zero, then the eight flags gathered into one byte by a multiplication
-                uint8_t *w = reinterpret_cast<uint8_t *>(bits.data() + (size_t)b * nw);   // zero-initialised; little-endian host
-                int64_t i = 0;
-                for (; i + 8 <= ntree; i += 8) {
-                    uint64_t v;
-                    memcpy(&v, t + i, 8);
-                    v = ((((v & 0x7f7f7f7f7f7f7f7fULL) + 0x7f7f7f7f7f7f7f7fULL) | v) & 0x8080808080808080ULL) >> 7;
-                    w[i >> 3] = (uint8_t)((v * 0x0102040810204080ULL) >> 56);
-                }
-                for (; i < ntree; ++i) w[i >> 3] |= (uint8_t)((t[i] != 0) << (i & 7));
-            }
+            if (lds_path) wt_pack_host(t, ntree, bits.data() + (size_t)b * nw);    // zero-initialised
         }
     };
     unsigned nth = 1;
@@ -285,17 +362,7 @@ int api_wpt_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int6
         (void)hipStreamSynchronize(st);
         return io.finish(wx_set_hip_error(e, "wptall(trees): tree upload", __FILE__, __LINE__));
     }
-    const size_t lds = wt_lds_bytes<T>(n);
-    const int nt = wt_threads(n);
-    auto kern = k_wpt_trees<T, MODE>;
-    if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) {
-        int log2n = 0;
-        while (((int64_t)1 << log2n) < n) ++log2n;
-        hipLaunchKernelGGL(kern, dim3(wt_grid(lds, nt, batch)), dim3(nt), lds, st, dx, dy, log2n, k, batch, (const uint32_t *)dt,
-                           (const uint8_t *)dd, filt);
-        e = hipGetLastError();
-    }
+    e = wt_launch<T, MODE>(dx, dy, n, k, batch, (const uint32_t *)dt, dd, filt, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);                 // `bits` and `depths` are released on return
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);

@@ -7,18 +7,25 @@ there is no CPU path.
 import numpy as np
 
 from . import _lib
-from ._arrays import Arg, out_arg, qmf_arg, tree_arg
+from ._arrays import Arg, is_torch, out_arg, qmf_arg, tree_arg, trees_arg
 from .util import isdyadic, maxtransformlevels
 
 
+def _is_device_trees(a):
+    """a matrix of per-signal trees in device memory (bestbasistreeall(X, BB(), device=True))"""
+    return is_torch(a) and a.device.type != "cpu" and a.dim() == 2
+
+
 def _is_tree(a):
-    return isinstance(a, np.ndarray) or (isinstance(a, (list, tuple)) and len(a) and isinstance(a[0], (bool, np.bool_)))
+    return isinstance(a, np.ndarray) or _is_device_trees(a) or (isinstance(a, (list, tuple)) and len(a) and isinstance(a[0], (bool, np.bool_)))
 
 
 def _split_Ltree(arg, default_L):
     """(L | tree | missing) -> (L, tree)"""
     if arg is None:
         return int(default_L), None
+    if _is_device_trees(arg):
+        return 0, arg
     if _is_tree(arg):
         return 0, np.asarray(arg, dtype=bool)
     return int(arg), None
@@ -55,20 +62,11 @@ def _wpt_batched(name, x, y, sig_ndim, wt, L, tree):
         _call(name + "2d", x.suffix, x.ptr, y.ptr, m, n, L, tp, nt, B, qp, F, x.stream())
 
 
-def _trees_arg(trees, B):
-    """one tree per signal, (n-1, B) booleans (what bestbasistreeall(X, BB()) returns) -> (uint8 buffer kept alive, pointer, rows)"""
-    import ctypes
-    assert B == trees.shape[1]                                        # Utils.jl:210, the BitMatrix convention of getbasiscoefall
-    tb = np.asfortranarray(trees)                                     # column i = the tree of signal i
-    tb = tb.view(np.uint8) if tb.dtype == np.bool_ else tb.astype(np.uint8)   # booleans are bytes of 0 / 1 already: no copy
-    return tb, ctypes.c_void_p(tb.ctypes.data), int(tb.shape[0])
-
-
 def _wpt_trees(name, x, y, wt, trees):
     """wptall / iwptall with one tree per signal (1-D): csrc/wx_wpt_trees.hip"""
     q, qp, F = qmf_arg(wt)
     n, B = x.shape[0], int(np.prod(x.shape[1:], dtype=np.int64))
-    tb, tp, nt = _trees_arg(trees, B)
+    tb, tp, nt = trees_arg(trees, B, x)
     _call(name + "1d_trees", x.suffix, x.ptr, y.ptr, n, tp, nt, B, qp, F, x.stream())
 
 
@@ -76,7 +74,7 @@ def _iwpd_trees(xw, xh, wt, trees):
     q, qp, F = qmf_arg(wt)
     n, k = xw.shape[0], xw.shape[1]
     B = int(np.prod(xw.shape[2:], dtype=np.int64))
-    tb, tp, nt = _trees_arg(trees, B)
+    tb, tp, nt = trees_arg(trees, B, xw)
     _call("wx_iwpd1d_trees", xw.suffix, xw.ptr, xh.ptr, n, k, tp, nt, B, qp, F, xw.stream())
 
 
@@ -162,6 +160,8 @@ def iwpdall(xw, wt, L_or_tree=None):
     sz, N = xw.shape[:-2], xw.shape[-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     xh = xw.new(sz + (N,))
+    if _is_device_trees(tree) and len(sz) != 1:
+        raise TypeError("device tree matrices are taken for 1-D signals only")
     if tree is not None and tree.ndim == 2 and len(sz) == 1:
         _iwpd_trees(xw, xh, wt, tree)
         return xh.arr
@@ -207,6 +207,8 @@ def _wptall_like(name, x, wt, L_or_tree):
     sz = x.shape[:-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     y = x.new(x.shape)
+    if _is_device_trees(tree) and len(sz) != 1:
+        raise TypeError("device tree matrices are taken for 1-D signals only")
     if tree is not None and tree.ndim == 2 and len(sz) == 1:
         _wpt_trees(name, x, y, wt, tree)
         return y.arr
@@ -216,7 +218,8 @@ def _wptall_like(name, x, wt, L_or_tree):
 
 def wptall(x, wt, L_or_tree=None):
     """dwt/dwt_all.jl:152-166.  1-D signals also take one tree per signal, a boolean (n-1, N) matrix in place of `L | tree`:
-    the result is getbasiscoefall(wpdall(x, wt), trees) without the table."""
+    the result is getbasiscoefall(wpdall(x, wt), trees) without the table.  The matrix may be a device tensor of torch.bool /
+    torch.uint8 (bestbasistreeall(X, BB(), device=True)) next to device data: it is checked and packed on the device."""
     return _wptall_like("wx_wpt", x, wt, L_or_tree)
 
 
@@ -300,9 +303,25 @@ def getbasiscoef(Xw, tree):
     return out.arr
 
 
+def _getbasiscoefall_device_trees(Xw, trees):
+    """getbasiscoefall with the trees in device memory: validated there, read by the gather where they are (csrc/wx_trees_prep.hip)"""
+    sig, k, N = Xw.shape[:-2], Xw.shape[-2], Xw.shape[-1]
+    tb, tp, nt = trees_arg(trees, N, Xw)
+    out = Xw.new(sig + (N,))
+    if len(sig) == 2:
+        _call("wx_getbasiscoef2d_trees", Xw.suffix, Xw.ptr, out.ptr, sig[0], sig[1], k, tp, nt, N, Xw.stream())
+    else:
+        _call("wx_getbasiscoef1d_trees", Xw.suffix, Xw.ptr, out.ptr, sig[0], k, tp, nt, N, Xw.stream())
+    return out.arr
+
+
 def getbasiscoefall(Xw, tree):
+    """Utils.jl:169-225.  One tree per signal: a boolean (tree length, N) matrix, or a device tensor of torch.bool / torch.uint8
+    of that shape (bestbasistreeall(X, BB(), device=True)), which stays on the device."""
     Xw = Arg(Xw)
     assert 3 <= Xw.arr.ndim <= 4                                      # Utils.jl:175
+    if _is_device_trees(tree):
+        return _getbasiscoefall_device_trees(Xw, tree)
     tree = np.asarray(tree, dtype=bool)
     if Xw.arr.ndim == 4:
         mm, nn, k, N = Xw.shape

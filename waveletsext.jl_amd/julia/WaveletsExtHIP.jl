@@ -367,6 +367,41 @@ function iwpdall(xw::HIP{T,3}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
     return x̂
 end
 
+# The same four with the trees as bytes under the marker wrapper, `trees::HIP{UInt8,2}`: the wrapped matrix crosses as its pointer,
+# without the Matrix{UInt8} conversion.  It may be a device array -- what bestbasistreeall(X, method; device = true) returns -- and
+# is then checked (and, for the transforms, packed) on the device: csrc/wx_trees_prep.hip; only a status record comes back.
+function getbasiscoefall(Xw::HIP{T}, trees::HIP{UInt8,2}) where T<:FT
+    @assert 3 ≤ ndims(Xw) ≤ 4
+    sz = size(Xw)[1:end-2]; k = size(Xw)[end-1]; N = size(Xw)[end]
+    @assert size(trees, 2) == N
+    out = newlike(Xw, T, (sz..., N))
+    c_getbasiscoef_trees(T, raw(Xw), out, sz, k, raw(trees), size(trees, 1), N)
+    return out
+end
+function wptall(x::HIP{T,2}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    n, N = size(x)
+    @assert size(trees, 2) == N
+    y = newlike(x, T, size(x))
+    c_wpt_trees(T, raw(x), y, n, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return y
+end
+function iwptall(xw::HIP{T,2}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    n, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, size(xw))
+    c_iwpt_trees(T, raw(xw), x̂, n, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return x̂
+end
+function iwpdall(xw::HIP{T,3}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, (n, N))
+    c_iwpd_trees(T, raw(xw), x̂, n, k, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return x̂
+end
+"the way the last call with one tree per signal went on this thread (wx_wpt_trees_last_route, include/waveletsext_hip.h)"
+wpt_trees_route() = (:none, :host, :device_lds, :device_single, :device_copied, :device_gather)[Int(wx_wpt_trees_last_route()) + 1]
+
 # ---------------------------------------------------------------------------------------------------------------------
 # stationary transforms -- SWT.jl, swt/swt_all.jl (1-D and 2-D)
 # ---------------------------------------------------------------------------------------------------------------------
@@ -637,11 +672,20 @@ function lsdb_entropy(X::HIP{T}) where T<:FT
     check(wx_lsdb_entropy(T, raw(X), length(E), size(X)[end], E, stream()))
     return reshape(E, size(X)[1:end-1])
 end
-# bestbasistreeall(X, BB) (BestBasis.jl:253-262): the costs of every signal and all N trees in one launch each
-function bestbasistreeall(X::HIP{T}, method::BB) where T<:FT
+# bestbasistreeall(X, BB) (BestBasis.jl:253-262): the costs of every signal and all N trees in one launch each.
+# device = true: costs and trees are arrays of the parent's kind (on a device array nothing leaves the device) and the trees come
+# back as the selection wrote them, a UInt8 matrix under the marker wrapper: the argument of the `trees::HIP{UInt8,2}` methods.
+function bestbasistreeall(X::HIP{T}, method::BB; device::Bool = false) where T<:FT
     @assert 3 ≤ ndims(X) ≤ 4
     sig = size(X)[1:end-2]; k = size(X)[end-1]; N = size(X)[end]
     ncost = jbb_ncost(sig, k, method.redundant)
+    if device
+        dcosts = newlike(X, T, (ncost, N))
+        c_bb_costs(T, raw(X), dcosts, sig, k, N, method.redundant, bbkind(method.cost))
+        dtrees = newlike(X, UInt8, (treelen(sig), N))
+        check(wx_treeselect_batch(T, dcosts, ncost, sig[1], length(sig) == 2 ? sig[2] : 0, 0, N, dtrees, stream()))
+        return HIP(dtrees)
+    end
     costs = Matrix{T}(undef, ncost, N)
     c_bb_costs(T, raw(X), costs, sig, k, N, method.redundant, bbkind(method.cost))
     trees = Matrix{UInt8}(undef, treelen(sig), N)
