@@ -1244,7 +1244,14 @@ def siwt_bestbasistree(obj):
             obj.Nodes[index]["Cost"] = float(ss)
         return obj.Nodes[index]["Cost"]
 
-    select((0, 0, 0))
+    # siwt_delete_node filters the whole BestTree list for every node it deletes, which makes the selection
+    # quadratic in the number of nodes; the selection itself reads Nodes only, so the list is set aside and
+    # filtered once (same order, same result)
+    order, obj.BestTree = obj.BestTree, []
+    try:
+        select((0, 0, 0))
+    finally:
+        obj.BestTree = [t for t in order if t in obj.Nodes]
     obj.MinCost = obj.Nodes[(0, 0, 0)]["Cost"]
     assert siwt_isvalidtree(obj)
     return obj.BestTree
