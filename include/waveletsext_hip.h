@@ -289,7 +289,34 @@ int wx_iwpd1d_trees_f64(const double *xw, double *xhat, int64_t n, int k, const 
 int wx_iwpd1d_trees_f32(const float *xw, float *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream);
 
-/* Per-signal tree matrices: `trees` of the ten wx_*_trees_* entries above is host or device memory, told apart like the data
+/* The same three for IMAGES with ONE quad tree per image: the reference's 2-D wpt! / iwpt! / iwpd! (DWT.jl:500-548, 662-710,
+ * 340-401) applied to image b with the quad tree in column b of `trees` (heap order, children 4i-2 .. 4i+1 = top-left (low/low),
+ * top-right, bottom-left, bottom-right; dwt_step! transforms all columns first, then the rows, dwt/dwt_one_level.jl:319-354).
+ * x, y, xhat: (m, n, batch) column-major; iwpd: xw (m, n, k, batch).  trees: host or device pointer, (ntree, batch) bytes, exactly
+ * as wx_getbasiscoef2d_trees_*; a HOST matrix may be released on return.  Data pointers may be host or device.
+ * Checked before anything is launched or written, and before a device is needed, the lowest offending column deciding: bad
+ * dimensions WX_EARG; NULL trees with batch > 0 WX_EARG; x == y (xw == xhat) WX_EARG: in-place calls are NOT supported; ntree ==
+ * gettreelength(m, n) (WX_EASSERT); every column a valid quad tree (WX_EASSERT, Utils.jl:209) no deeper than both sides divide by
+ * (WX_EASSERT, as the single-tree entries); iwpd: every tree's depth < k (WX_EARG, Utils.jl:120).  batch == 0 is WX_OK.
+ * Both sides dyadic and >= 8, m n <= 8192 (Float64) / 16384 (Float32), an even filter of 2 .. 20 taps: one launch, a workgroup per
+ * image with the image and its tree in LDS (csrc/wx_wpt_trees2d.hip).  Anything else is computed by the single-tree 2-D entry
+ * called once per image inside the library: correct and slow.  Byte-identical columns are handed to the single-tree entry whole.
+ * Every leaf of wx_wpt2d_trees_* sits at its node's own row and column range, i.e. y equals wx_getbasiscoef2d_trees_* of the
+ * wx_wpd2d_* table up to rounding. */
+int wx_wpt2d_trees_f64(const double *x, double *y, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                       const double *qmf, int F, void *stream);
+int wx_wpt2d_trees_f32(const float *x, float *y, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                       const double *qmf, int F, void *stream);
+int wx_iwpt2d_trees_f64(const double *xw, double *xhat, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+int wx_iwpt2d_trees_f32(const float *xw, float *xhat, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                        const double *qmf, int F, void *stream);
+int wx_iwpd2d_trees_f64(const double *xw, double *xhat, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree,
+                        int64_t batch, const double *qmf, int F, void *stream);
+int wx_iwpd2d_trees_f32(const float *xw, float *xhat, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree,
+                        int64_t batch, const double *qmf, int F, void *stream);
+
+/* Per-signal tree matrices: `trees` of the sixteen wx_*_trees_* entries above is host or device memory, told apart like the data
  * pointers (hipPointerGetAttributes); any non-zero byte means "decomposed".  A host matrix is handled as before.  A DEVICE matrix
  * -- the output of wx_treeselect_batch_* on device costs, never copied back -- follows these rules:
  *  - it must live on the current device, else WX_EARG; the argument checks that need no tree content (dimensions, NULL, aliasing,
@@ -297,14 +324,14 @@ int wx_iwpd1d_trees_f32(const float *xw, float *xhat, int64_t n, int k, const ui
  *  - one launch (csrc/wx_trees_prep.hip) checks every column (valid tree: WX_EASSERT; depth < k where the entry has a k: WX_EARG;
  *    the lowest offending column decides, as on the host), and the call waits for its stream ONCE, to read that launch's status
  *    record; errors from the tree content are reported before any output element is written;
- *  - wx_wpt1d_trees_* / wx_iwpt1d_trees_* / wx_iwpd1d_trees_* inside the LDS kernel's window (above): the same launch packs the
+ *  - wx_wpt1d_trees_* / wx_iwpt1d_trees_* / wx_iwpd1d_trees_* and their 2-D forms inside their LDS kernel's window (above): the same launch packs the
  *    trees into the kernel's bit layout and notes their depths; the matrix never reaches the host, and with device data the call
  *    returns with the transform queued.  All columns equal byte for byte: column 0 (ntree bytes) goes to the host and the
  *    single-tree entry runs, so the result is the host route's.  Outside the window the matrix is copied to the host once and
  *    the host route runs: correct and slow;
  *  - wx_getbasiscoef1d_trees_* / wx_getbasiscoef2d_trees_*: the gather reads the caller's matrix; with device data the call returns
  *    with the gather queued, so the matrix must stay valid until the stream has passed it.
- * wx_wpt_trees_last_route: the way the last of these ten calls went on the calling thread: 0 = none yet, or that call returned an
+ * wx_wpt_trees_last_route: the way the last of these sixteen calls went on the calling thread: 0 = none yet, or that call returned an
  * error; 1 = host trees; 2 = device trees, prep launch + LDS kernel; 3 = device trees, prep launch + single-tree entry;
  * 4 = device trees copied to the host (outside the window); 5 = device trees, prep launch + gather. */
 int wx_wpt_trees_last_route(void);

@@ -17,7 +17,7 @@ void wx_trees_route_set(int route);
 // One launch over the (ntree, batch) byte matrix `trees` (device memory of the current device, any non-zero byte = decomposed;
 // quad = false: binary heap, children 2i and 2i + 1; quad = true: children 4i - 2 .. 4i + 1) and ONE wait for the stream:
 //   every column is a valid tree, else WX_EASSERT; k > 0: every depth < k, else WX_EARG; the lowest offending column decides;
-//   bits   != nullptr (1-D): the columns in the layout of wx_tree_bits.h, nw words each;
+//   bits   != nullptr: the columns in the layout of wx_tree_bits.h (node i is bit i - 1, either heap), nw words each, every word written;
 //   depths != nullptr: one byte per column, the depth of the deepest decomposed node + 1 (0 for the bare root);
 //   same   != nullptr: whether every column equals column 0 byte for byte, and col0 (ntree bytes, host) receives that column.
 // Returns WX_OK, the two codes above (message set) or WX_EHIP.  ntree == 0: nothing to check, *same = true.

@@ -62,20 +62,26 @@ def _wpt_batched(name, x, y, sig_ndim, wt, L, tree):
         _call(name + "2d", x.suffix, x.ptr, y.ptr, m, n, L, tp, nt, B, qp, F, x.stream())
 
 
-def _wpt_trees(name, x, y, wt, trees):
-    """wptall / iwptall with one tree per signal (1-D): csrc/wx_wpt_trees.hip"""
+def _wpt_trees(name, x, y, sig_ndim, wt, trees):
+    """wptall / iwptall with one tree per signal (csrc/wx_wpt_trees.hip) or one quad tree per image (csrc/wx_wpt_trees2d.hip)"""
     q, qp, F = qmf_arg(wt)
-    n, B = x.shape[0], int(np.prod(x.shape[1:], dtype=np.int64))
+    B = int(np.prod(x.shape[sig_ndim:], dtype=np.int64))
     tb, tp, nt = trees_arg(trees, B, x)
-    _call(name + "1d_trees", x.suffix, x.ptr, y.ptr, n, tp, nt, B, qp, F, x.stream())
+    if sig_ndim == 1:
+        _call(name + "1d_trees", x.suffix, x.ptr, y.ptr, x.shape[0], tp, nt, B, qp, F, x.stream())
+    else:
+        _call(name + "2d_trees", x.suffix, x.ptr, y.ptr, x.shape[0], x.shape[1], tp, nt, B, qp, F, x.stream())
 
 
-def _iwpd_trees(xw, xh, wt, trees):
+def _iwpd_trees(xw, xh, sig_ndim, wt, trees):
     q, qp, F = qmf_arg(wt)
-    n, k = xw.shape[0], xw.shape[1]
-    B = int(np.prod(xw.shape[2:], dtype=np.int64))
+    k = xw.shape[sig_ndim]
+    B = int(np.prod(xw.shape[sig_ndim + 1:], dtype=np.int64))
     tb, tp, nt = trees_arg(trees, B, xw)
-    _call("wx_iwpd1d_trees", xw.suffix, xw.ptr, xh.ptr, n, k, tp, nt, B, qp, F, xw.stream())
+    if sig_ndim == 1:
+        _call("wx_iwpd1d_trees", xw.suffix, xw.ptr, xh.ptr, xw.shape[0], k, tp, nt, B, qp, F, xw.stream())
+    else:
+        _call("wx_iwpd2d_trees", xw.suffix, xw.ptr, xh.ptr, xw.shape[0], xw.shape[1], k, tp, nt, B, qp, F, xw.stream())
 
 
 def _iwpd_batched(xw, xh, sig_ndim, wt, L, tree):
@@ -154,16 +160,17 @@ def iwpd_(xh, xw, wt, L_or_tree=None):
 
 def iwpdall(xw, wt, L_or_tree=None):
     """dwt/dwt_all.jl:324-342: iwpd!(x̂ᵢ, xwᵢ, args...) over the last dimension.  1-D signals also take one tree per signal, a
-    boolean (n-1, N) matrix in place of `L | tree` (the BitMatrix convention of getbasiscoefall, Utils.jl:199-225)."""
+    boolean (n-1, N) matrix in place of `L | tree` (the BitMatrix convention of getbasiscoefall, Utils.jl:199-225); images
+    (an (m, n, k, N) table) one quad tree per image, a (gettreelength(m, n), N) matrix.  Either may be a device tensor, as in wptall."""
     xw = Arg(xw)
     assert xw.arr.ndim > 2
     sz, N = xw.shape[:-2], xw.shape[-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     xh = xw.new(sz + (N,))
-    if _is_device_trees(tree) and len(sz) != 1:
-        raise TypeError("device tree matrices are taken for 1-D signals only")
-    if tree is not None and tree.ndim == 2 and len(sz) == 1:
-        _iwpd_trees(xw, xh, wt, tree)
+    if _is_device_trees(tree) and len(sz) > 2:
+        raise TypeError("device tree matrices are taken for 1-D signals and images")
+    if tree is not None and tree.ndim == 2 and len(sz) <= 2:
+        _iwpd_trees(xw, xh, len(sz), wt, tree)
         return xh.arr
     _iwpd_batched(xw, xh, len(sz), wt, L, tree)
     return xh.arr
@@ -207,10 +214,10 @@ def _wptall_like(name, x, wt, L_or_tree):
     sz = x.shape[:-1]
     L, tree = _split_Ltree(L_or_tree, maxtransformlevels(int(min(sz))))
     y = x.new(x.shape)
-    if _is_device_trees(tree) and len(sz) != 1:
-        raise TypeError("device tree matrices are taken for 1-D signals only")
-    if tree is not None and tree.ndim == 2 and len(sz) == 1:
-        _wpt_trees(name, x, y, wt, tree)
+    if _is_device_trees(tree) and len(sz) > 2:
+        raise TypeError("device tree matrices are taken for 1-D signals and images")
+    if tree is not None and tree.ndim == 2 and len(sz) <= 2:
+        _wpt_trees(name, x, y, len(sz), wt, tree)
         return y.arr
     _wpt_batched(name, x, y, len(sz), wt, L, tree)
     return y.arr
@@ -219,12 +226,13 @@ def _wptall_like(name, x, wt, L_or_tree):
 def wptall(x, wt, L_or_tree=None):
     """dwt/dwt_all.jl:152-166.  1-D signals also take one tree per signal, a boolean (n-1, N) matrix in place of `L | tree`:
     the result is getbasiscoefall(wpdall(x, wt), trees) without the table.  The matrix may be a device tensor of torch.bool /
-    torch.uint8 (bestbasistreeall(X, BB(), device=True)) next to device data: it is checked and packed on the device."""
+    torch.uint8 (bestbasistreeall(X, BB(), device=True)) next to device data: it is checked and packed on the device.
+    Images, an (m, n, N) array, take one quad tree per image in the same way: a (gettreelength(m, n), N) matrix, host or device."""
     return _wptall_like("wx_wpt", x, wt, L_or_tree)
 
 
 def iwptall(xw, wt, L_or_tree=None):
-    """dwt/dwt_all.jl:210-225.  1-D signals also take one tree per signal, as wptall."""
+    """dwt/dwt_all.jl:210-225.  1-D signals also take one tree per signal and images one quad tree per image, as wptall."""
     return _wptall_like("wx_iwpt", xw, wt, L_or_tree)
 
 

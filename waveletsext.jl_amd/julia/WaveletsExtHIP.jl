@@ -113,6 +113,9 @@ c_getbasiscoef_trees(T, Xw, out, sig::NTuple{2,Int}, k, tb, nt, N) =
 c_wpt_trees(T, x, y, n, tb, nt, N, q) = check(wx_wpt1d_trees(T, x, y, n, tb, nt, N, q, length(q), stream()))
 c_iwpt_trees(T, xw, x, n, tb, nt, N, q) = check(wx_iwpt1d_trees(T, xw, x, n, tb, nt, N, q, length(q), stream()))
 c_iwpd_trees(T, xw, x, n, k, tb, nt, N, q) = check(wx_iwpd1d_trees(T, xw, x, n, k, tb, nt, N, q, length(q), stream()))
+c_wpt_trees2d(T, x, y, m, n, tb, nt, N, q) = check(wx_wpt2d_trees(T, x, y, m, n, tb, nt, N, q, length(q), stream()))
+c_iwpt_trees2d(T, xw, x, m, n, tb, nt, N, q) = check(wx_iwpt2d_trees(T, xw, x, m, n, tb, nt, N, q, length(q), stream()))
+c_iwpd_trees2d(T, xw, x, m, n, k, tb, nt, N, q) = check(wx_iwpd2d_trees(T, xw, x, m, n, k, tb, nt, N, q, length(q), stream()))
 c_dwt3d(T, x, y, sig::NTuple{3,Int}, L, N, q) = check(wx_dwt3d(T, x, y, sig[1], sig[2], sig[3], L, N, q, length(q), stream()))
 c_idwt3d(T, x, y, sig::NTuple{3,Int}, L, N, q) = check(wx_idwt3d(T, x, y, sig[1], sig[2], sig[3], L, N, q, length(q), stream()))
 
@@ -397,6 +400,54 @@ function iwpdall(xw::HIP{T,3}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
     @assert size(trees, 2) == N
     x̂ = newlike(xw, T, (n, N))
     c_iwpd_trees(T, raw(xw), x̂, n, k, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return x̂
+end
+# Images with one QUAD tree per image (csrc/wx_wpt_trees2d.hip): column i of `trees` (gettreelength(m, n) rows, what
+# bestbasistreeall returns for an (m, n, k, N) table) is the tree of image i.  The BitMatrix goes over as bytes; bytes under the
+# marker wrapper cross as their pointer and may live on the device, exactly as in 1-D.
+function wptall(x::HIP{T,3}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    m, n, N = size(x)
+    @assert size(trees, 2) == N
+    y = newlike(x, T, size(x))
+    tb = Matrix{UInt8}(trees)
+    c_wpt_trees2d(T, raw(x), y, m, n, tb, size(tb, 1), N, qmfvec(wt))
+    return y
+end
+function iwptall(xw::HIP{T,3}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    m, n, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, size(xw))
+    tb = Matrix{UInt8}(trees)
+    c_iwpt_trees2d(T, raw(xw), x̂, m, n, tb, size(tb, 1), N, qmfvec(wt))
+    return x̂
+end
+function iwpdall(xw::HIP{T,4}, wt::OrthoFilter, trees::BitMatrix) where T<:FT
+    m, n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, (m, n, N))
+    tb = Matrix{UInt8}(trees)
+    c_iwpd_trees2d(T, raw(xw), x̂, m, n, k, tb, size(tb, 1), N, qmfvec(wt))
+    return x̂
+end
+function wptall(x::HIP{T,3}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    m, n, N = size(x)
+    @assert size(trees, 2) == N
+    y = newlike(x, T, size(x))
+    c_wpt_trees2d(T, raw(x), y, m, n, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return y
+end
+function iwptall(xw::HIP{T,3}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    m, n, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, size(xw))
+    c_iwpt_trees2d(T, raw(xw), x̂, m, n, raw(trees), size(trees, 1), N, qmfvec(wt))
+    return x̂
+end
+function iwpdall(xw::HIP{T,4}, wt::OrthoFilter, trees::HIP{UInt8,2}) where T<:FT
+    m, n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, (m, n, N))
+    c_iwpd_trees2d(T, raw(xw), x̂, m, n, k, raw(trees), size(trees, 1), N, qmfvec(wt))
     return x̂
 end
 "the way the last call with one tree per signal went on this thread (wx_wpt_trees_last_route, include/waveletsext_hip.h)"
