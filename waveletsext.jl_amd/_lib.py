@@ -260,6 +260,31 @@ def lattice_fold_matrix(qmf, nf, inverse=True):
     return m if got == nf else None
 
 
+LatticeFactor = collections.namedtuple("LatticeFactor", "p kap g0 g2")
+
+
+def lattice_factor(qmf, L, inverse=False, elem_size=8):
+    """csrc/wx_debug.h: the launchers' own lattice factorisation of the QMF for a transform of L levels -- the shears p[j], kap[j]
+    (F / 2 of them) and the gains g0 = g^(+-L), g2 = g^(-+2) -- or None when it declines (the direct-form kernels run).
+    elem_size 8: kernels with Float64 registers; 4: kernels that compute in Float32 and normalise once after L levels, which
+    also decline a gain g^(L + 1) below 2^-50 and shears too ill-conditioned for L levels of Float32 (the
+    tree-driven Float32 kernels normalise every level and apply the range rule of one level)."""
+    import numpy as np
+    q = np.ascontiguousarray(qmf, dtype=np.float64)
+    p = np.zeros(10, dtype=np.float64)
+    kap = np.zeros(10, dtype=np.float64)
+    g0, g2 = ctypes.c_double(0.0), ctypes.c_double(0.0)
+    f = lib().wx_debug_lattice_factor
+    f.argtypes = [_P, _I, _I, _I, _I, _P, _P, _P, _P]
+    f.restype = _I
+    ok = f(q.ctypes.data, int(q.size), int(L), 1 if inverse else 0, int(elem_size), p.ctypes.data, kap.ctypes.data,
+           ctypes.addressof(g0), ctypes.addressof(g2))
+    if not ok:
+        return None
+    ns = q.size // 2
+    return LatticeFactor(p[:ns].copy(), kap[:ns].copy(), g0.value, g2.value)
+
+
 RED2D_ROUTES = {1: "F1", 2: "F2", 3: "F3", 4: "I1", 5: "I2", 6: "I3", 7: "I4"}
 
 

@@ -14,6 +14,13 @@ void wx_debug_set_dispatch(int mode);
  * the QMF q of length F, as the launchers build it (wx_lattice_fold_matrix).  Returns NF, or 0 when this filter does not fold. */
 int wx_debug_lattice_fold(const double *q, int F, int NF, int inverse, double *m);
 
+/* The lattice factorisation of the QMF q of length F as the launchers run it for a transform of L levels (wx_lattice_factor for
+ * elem_size 8: kernels with Float64 registers; wx_lattice_factor32 with LW = L for elem_size 4: kernels that compute in Float32 and
+ * normalise once -- the tree-driven Float32 kernels normalise every level and apply the window of L = 1).  p and kap receive 10
+ * values (zero past F / 2), g0 = g^(+-L), g2 = g^(-+2).  Returns 1 = accepted, 0 = declined (the direct-form kernels run) or
+ * arguments outside 2 <= F <= 64, L >= 1.  Needs no device. */
+int wx_debug_lattice_factor(const double *q, int F, int L, int inverse, int elem_size, double *p, double *kap, double *g0, double *g2);
+
 /* Which kernels the 2-D redundant transforms (wx_swt2d.hip) launch under the current dispatch mode; computed by the very
  * function the launch code calls.  elem_size 8 / 4 = Float64 / Float32, F = filter length, ac = autocorrelation family,
  * shift = shift-based inverse (sm given).  Returns route + 256 * R, or -1 for arguments outside the transforms' domain:

@@ -5,8 +5,9 @@
 
 // Lattice factorisation of the polyphase matrix (long double): G(w) = [[Qe, Qo], [-w^J Qo(1/w), w^J Qe(1/w)]]
 // = R_J Lambda(w) R_{J-1} ... Lambda(w) R_0 with R_j = c_j [[1, t_j], [-t_j, 1]], Lambda = diag(1, w).
-// Returns false when a rotation is too close to a quarter turn (|t| huge) or the rebuilt filter misses q.
-bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out)
+// Returns false when a rotation is too close to a quarter turn (|t| huge) or the rebuilt filter misses q; *gain = g = prod c_j,
+// *cond = sum_j 1 / c_j^2.
+static bool lat_factor_core(const WxFilt &filt, int L, bool inverse, WxLat *out, long double *gain, long double *cond)
 {
     const int F = filt.F;
     if (F < 2 || (F & 1) || F / 2 > WX_LAT_MAXS) return false;
@@ -89,8 +90,51 @@ bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out)
     const long double gL = powl(gain1, L);
     out->g0 = (double)(inverse ? 1 / gL : gL);
     out->g2 = (double)(inverse ? gain1 * gain1 : 1 / (gain1 * gain1));
-    // the intermediate values range over g^(+-L): keep them far from the limits of Float64
-    return std::isfinite(out->g0) && fabsl(gL) > 1e-60L && fabsl(gL) < 1e60L;
+    *gain = gain1;
+    *cond = 0;
+    for (int j = 0; j <= J; ++j) *cond += 1 + t[j] * t[j];
+    return std::isfinite(out->g0);
+}
+
+// What the kernels' arithmetic can carry.  They apply the rotations unnormalised: with g = prod c_j (|g| <= 1), LW levels after the
+// last normalisation an a-slot holds a / g^LW and a d-slot d g^LW, and inside the next level the odd channel carries sigma_j v with
+// sigma_j >= g^2, so a register ranges over value * |g|^-LW ... value * |g|^(LW + 1).  LW = L for the kernels that normalise once,
+// at the leaves (g0 = g^(+-L)); LW = 1 for the tree-driven kernels, which normalise every level.  LT = the levels a sample passes
+// through in that arithmetic (L; 2 L for an image).
+//   Float64 registers: g^L within 1e+-60, far from the limits of the format for any Float32 array and for Float64 arrays within
+//   2^+-400 of unit scale; every |c_j| >= 1e-3 (lat_factor_core), see the conditioning below: 1.1e-16 / 1e-3 per shear.
+//   Float32 arithmetic (lat_f2v pairs, wx_lattice2d.h), two conditions ("What the lattice declines"):
+//   Range, (LW + 1) log2 |g| >= -50.  Guaranteed input range: 2^-40 <= max |x| <= 2^40.  Top: a coefficient is at most
+//   sqrt(n) max |x| <= 2^10 * 2^40 (n <= 2^20 samples), an unnormalised rotation adds a factor sqrt(2), so a register stays below
+//   2^50.5 |g|^-LW <= 2^100.5 < 2^127.  Bottom: a result below 2^-126 may be flushed, an absolute error of 2^-126 |g|^-(LW + 1)
+//   in the units of the signal.  At most 2^6 such errors meet in one output (10 rotations in each of the last levels; the earlier
+//   levels' shrink by |g| per level), and the largest coefficient is at least max |x| / sqrt(n) >= 2^-50: 2^6 * 2^-126 * 2^50 =
+//   2^-70 is 2^-20 of it, a tenth of the 1e-5 the Float32 results are held to.
+//   Conditioning, LT * sum_j (1 + t_j^2) <= 1000.  The second shear of rotation j, w -= kap_j u, subtracts sigma t^2 c^2 v from
+//   sigma v and keeps sigma c^2 (v - t u): it cancels all but c_j^2 of w, so the rounding of w (unit roundoff u = 2^-24, rms
+//   u / sqrt(3) = 3.4e-8 relative) returns as 3.4e-8 / |c_j| of the normalised sample.  The shears of LT levels add in quadrature
+//   to 3.4e-8 sqrt(LT sum_j 1 / c_j^2), 1 / c_j^2 = 1 + t_j^2; the largest of the 10^4 ... 10^7 samples of a call lies near 4.5
+//   standard deviations: 4.5 * 3.4e-8 * sqrt(1000) = 4.8e-6, half of the 1e-5; the other half is left to the roundings every
+//   Float32 form has, the reference's direct form among them.
+static bool lat_window(long double gain1, long double cond, int L, int LW, int LT, int elem_size)
+{
+    const long double gL = powl(gain1, L);
+    if (!(fabsl(gL) > 1e-60L && fabsl(gL) < 1e60L)) return false;
+    if (elem_size == 4 && !((LW + 1) * log2l(fabsl(gain1)) >= -50.0L && LT * cond <= 1000.0L)) return false;
+    return true;
+}
+
+bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out)
+{
+    long double g, cond;
+    return lat_factor_core(filt, L, inverse, out, &g, &cond) && lat_window(g, cond, L, L, L, 8);
+}
+
+// for the launchers of kernels that compute in Float32: LW = levels between two normalisations, LT = levels a sample passes through
+bool wx_lattice_factor32(const WxFilt &filt, int L, bool inverse, WxLat *out, int LW, int LT)
+{
+    long double g, cond;
+    return lat_factor_core(filt, L, inverse, out, &g, &cond) && lat_window(g, cond, L, LW, LT, 4);
 }
 
 // Node matrix of the deepest log2(NF) levels of a full-depth transform (wx_lattice_fold.h): the shear and advance recurrence of
@@ -152,11 +196,27 @@ extern "C" int wx_debug_lattice_fold(const double *q, int F, int NF, int inverse
     return wx_lattice_fold_matrix(cf, NS, NF, inverse != 0, m) ? NF : 0;
 }
 
-// the factorisation for other translation units (wx_lattice2d.hip): p[j], kap[j] (j < F/2), g0 = g^(+-L), g2 = g^(-+2)
+// test hook (wx_debug.h): the verdict and the coefficients of the launchers' own factorisation; 1 = accepted, 0 = declined
+extern "C" int wx_debug_lattice_factor(const double *q, int F, int L, int inverse, int elem_size, double *p, double *kap, double *g0, double *g2)
+{
+    if (!q || !p || !kap || !g0 || !g2 || F < 2 || F > WX_MAXF || L < 1 || (elem_size != 4 && elem_size != 8)) return 0;
+    WxFilt filt = {};
+    for (int i = 0; i < F; ++i) filt.q[i] = q[i];
+    filt.F = F;
+    WxLat c;
+    if (!(elem_size == 4 ? wx_lattice_factor32(filt, L, inverse != 0, &c, L, L) : wx_lattice_factor(filt, L, inverse != 0, &c))) return 0;
+    for (int j = 0; j < WX_LAT_MAXS; ++j) { p[j] = c.p[j]; kap[j] = c.kap[j]; }
+    *g0 = c.g0;
+    *g2 = c.g2;
+    return 1;
+}
+
+// the factorisation for other translation units (wx_lattice2d.hip: Float32 arithmetic, one normalisation after the L levels of a
+// pass, two passes over an image): p[j], kap[j] (j < F/2), g0 = g^(+-L), g2 = g^(-+2)
 bool wx_lattice_coeffs(const WxFilt &filt, int L, bool inverse, double *p, double *kap, double *g0, double *g2)
 {
     WxLat c;
-    if (!wx_lattice_factor(filt, L, inverse, &c)) return false;
+    if (!wx_lattice_factor32(filt, L, inverse, &c, L, 2 * L)) return false;
     for (int j = 0; j < WX_LAT_MAXS; ++j) { p[j] = c.p[j]; kap[j] = c.kap[j]; }
     *g0 = c.g0;
     *g2 = c.g2;
@@ -343,7 +403,13 @@ WX_T32(0, f) WX_T32(0, i) WX_T32(1, f) WX_T32(1, i) WX_T32(2, f) WX_T32(2, i)
 #undef WX_T32
 bool wx_lattice_tree_applicable_f32(int64_t n, const WxFilt &filt)
 {
-    return wx_lattice_tree_applicable_f64(n, filt);
+    if (!wx_lattice_tree_applicable_f64(n, filt)) return false;
+    if (n <= 512) return true;                                // wx_lattice_tree_s.h: what Float32 arithmetic declines runs in Float64 registers
+    // wx_lattice_tree32.h computes in Float32 only: applicable means that it takes every tree of these signals, down to the deepest
+    // (callers plan on the answer: the long signals of wx_dwt1d.hip have no other kernel behind their 4096-sample nodes)
+    const int Lmax = n == 4096 ? 12 : (n == 2048 ? 11 : 10);
+    WxLat tmp;
+    return wx_lattice_factor32(filt, Lmax, false, &tmp, 1, Lmax);
 }
 int wx_lattice_tree_f32(bool inverse, const float *x, float *y, int64_t n, int L, int64_t batch, int64_t in_stride, const WxFilt &filt,
                         const uint8_t *dstatus, int64_t nstatus, hipStream_t st, const WxThreshArg *thr, int64_t out_stride)

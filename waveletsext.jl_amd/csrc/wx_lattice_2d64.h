@@ -99,7 +99,8 @@ static int wx_lattice_2d64_launch(const IO *x, IO *y, int L, int64_t batch, int6
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return 0;
     if (in_img < 4096 || (in_img & 3) || in_img > 0x3fffffff) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, 2 * L, INV, &cw.c)) return 0;   // 2 L levels lie between an image and a coefficient: g0 = g^(2 L)
+    // 2 L levels lie between an image and a coefficient: g0 = g^(2 L)
+    if (!(PAIR ? wx_lattice_factor32(filt, 2 * L, INV, &cw.c, 2 * L, 2 * L) : wx_lattice_factor(filt, 2 * L, INV, &cw.c))) return 0;
     for (int l = 0; l <= 12; ++l) cw.gl[l] = 0.0;
     cw.gl[2 * L] = cw.c.g0;
     cw.gl[0] = 1.0;

@@ -203,7 +203,7 @@ static int wx_lattice_2d64t_launch(const IO *x, IO *y, int L, int64_t batch, int
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return 0;
     if (in_img < 4096 || (in_img & 3) || in_img > 0x3fffffff) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, INV, &cw.c)) return 0;
+    if (!(PAIR ? wx_lattice_factor32(filt, L, INV, &cw.c, 1, 2 * L) : wx_lattice_factor(filt, L, INV, &cw.c))) return 0;   // every level normalised
     {
         WxLat one;
         if (!wx_lattice_factor(filt, 1, false, &one)) return 0;

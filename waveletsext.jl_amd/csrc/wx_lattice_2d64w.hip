@@ -53,7 +53,7 @@ int wx_lattice_2d64_wpd_T(const IO *x, IO *y, int L, int64_t batch, const WxFilt
     if (L < 1 || L > 6 || filt.F < 2 || (filt.F & 1) || filt.F > 8 || batch < 1 || batch > 0x3fffffff || (const void *)x == (const void *)y) return 0;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, false, &cw.c)) return 0;
+    if (!(PAIR ? wx_lattice_factor32(filt, L, false, &cw.c, 2 * L, 2 * L) : wx_lattice_factor(filt, L, false, &cw.c))) return 0;   // slice l leaves with g^(2 l)
     {
         WxLat one;
         if (!wx_lattice_factor(filt, 1, false, &one)) return 0;

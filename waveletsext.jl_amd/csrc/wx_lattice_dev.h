@@ -1899,4 +1899,8 @@ __device__ __forceinline__ void lat_level_cm(V (&x)[64], const C &cf, const unsi
 
 }  // namespace
 
-bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out);      // wx_lattice.hip
+bool wx_lattice_factor(const WxFilt &filt, int L, bool inverse, WxLat *out);      // wx_lattice.hip: for kernels with Float64 registers
+// for kernels that compute in Float32 (V = lat_f2v): declines as well when the gain of LW unnormalised levels does not fit Float32
+// (LW = L where the leaves are normalised once, 2 L for the 64 x 64 images, 1 for the tree-driven kernels) or the shears of the LT
+// levels a sample passes through (L; 2 L for an image) are too ill-conditioned for it: wx_lattice.hip, lat_window
+bool wx_lattice_factor32(const WxFilt &filt, int L, bool inverse, WxLat *out, int LW, int LT);

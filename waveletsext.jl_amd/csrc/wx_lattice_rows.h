@@ -57,7 +57,7 @@ static int wx_lattice_rows_launch(const IO *x, IO *y, int64_t in_img, int64_t ou
     const int64_t groups = m / per, nwave = groups * batch;
     if (batch < 1 || nwave > 0x7fffffff || nwave % W) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, INV, &cw.c)) return 0;
+    if (!(PAIR ? wx_lattice_factor32(filt, L, INV, &cw.c, L, 2 * L) : wx_lattice_factor(filt, L, INV, &cw.c))) return 0;
     for (int l = 0; l <= 12; ++l) cw.gl[l] = 0.0;
     cw.gl[L] = cw.c.g0;
     cw.gl[0] = 1.0;

@@ -38,7 +38,7 @@ int WX_G32_FN(bool inverse, const float *x, float *y, int64_t n, int L, int64_t 
     if (in_stride * (per / 2) > 0x7fffffff) return 0;         // offset of the second signal set (32-bit element offsets)
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, inverse, &cw.c)) return 0;
+    if (!(PAIRS ? wx_lattice_factor32(filt, L, inverse, &cw.c, L, L) : wx_lattice_factor(filt, L, inverse, &cw.c))) return 0;
     for (int l = 0; l <= 12; ++l) cw.gl[l] = 0.0;
     cw.gl[L] = cw.c.g0;
     cw.gl[0] = 1.0;

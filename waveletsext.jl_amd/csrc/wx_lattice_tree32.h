@@ -25,7 +25,7 @@ int WX_LAT_TREE_FN(bool inverse, const float *x, float *y, int64_t n, int L, int
     if (ostr < n || (ostr & 3) || ostr * (2 * per - 1) + 4096 > 0x7fffffff) return 0;
     if (thr && thr->t) return 0;                             // the threshold of denoise() rides on the Float64 kernels only
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, inverse, &cw.c)) return 0;
+    if (!wx_lattice_factor32(filt, L, inverse, &cw.c, 1, L)) return 0;      // Float32 arithmetic, every level normalised (g, ginv of lat_level_cm)
     {
         WxLat one;
         if (!wx_lattice_factor(filt, 1, false, &one)) return 0;

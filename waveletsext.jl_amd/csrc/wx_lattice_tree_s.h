@@ -31,7 +31,7 @@ static int wx_lattice_trees_launch(const IO *x, IO *y, int64_t n, int L, int64_t
     const int64_t ostr = out_stride ? out_stride : n;
     if (ostr < n || (ostr & 3) || ostr * (2 * per - 1) + 4096 > 0x7fffffff) return 0;
     WxLatW cw;
-    if (!wx_lattice_factor(filt, L, INV, &cw.c)) return 0;
+    if (!(FP32A ? wx_lattice_factor32(filt, L, INV, &cw.c, 1, L) : wx_lattice_factor(filt, L, INV, &cw.c))) return 0;   // every level normalised
     {
         WxLat one;
         if (!wx_lattice_factor(filt, 1, false, &one)) return 0;
