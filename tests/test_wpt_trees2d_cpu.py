@@ -99,6 +99,35 @@ def test_iwpd_tree_deeper_than_the_table(wx, dtype):
     assert (a.y == 1).all()
 
 
+def test_sides_rule_in_column_order(wx):
+    """a tree deeper than both sides divide by is WX_EASSERT with the message of the sides, and the lowest offending column decides
+    between it and a tree that is too deep for the table.  Only a side that is not dyadic admits such a tree: 8 x 12 has 21 nodes,
+    12 = 4 * 3 takes two levels; on 8 x 32 the deepest tree of 21 nodes has depth 3 = min(log2 8, log2 32) and is no offender."""
+    lib = ctypes.CDLL(wx.LIB_PATH)
+    lib.wx_last_error.restype = ctypes.c_char_p
+    nt, B = 21, 5
+    a = _Abi(wx, np.float32, 8, 32, B, k=2)                            # buffers for either image
+    three, two, flat = _tree(nt, 1, 5, 21), _tree(nt, 1, 2), _tree(nt)   # depth 3: deeper than 12 divides; depth 2: too deep for k = 2
+    assert a.call("iwpd", 8, 12, _cols(flat, two, flat, three, flat), nt, B) == EARG          # behind a too deep one
+    assert b"Not enough decomposition levels" in lib.wx_last_error()
+    assert a.call("iwpd", 8, 12, _cols(flat, three, flat, two, flat), nt, B) == EASSERT       # and before it
+    assert b"both sides must be divisible" in lib.wx_last_error()
+    assert a.call("iwpd", 8, 12, _cols(flat, three, flat, flat, flat), nt, B) == EASSERT      # a column that is both: the sides first
+    assert b"both sides must be divisible" in lib.wx_last_error()
+    assert a.call("wpt", 8, 12, _cols(flat, two, flat, three, flat), nt, B) == EASSERT        # no k
+    assert b"both sides must be divisible" in lib.wx_last_error()
+    assert a.call("iwpd", 8, 32, _cols(flat, flat, flat, three, flat), nt, B) == EARG         # within the sides, below the table
+    assert b"Not enough decomposition levels" in lib.wx_last_error()
+    assert (a.y == 1).all()
+    # the gather has no such rule, its sides need not be dyadic: the same tree is too deep for a table of 3 slices, nothing else
+    fn = lib.wx_getbasiscoef2d_trees_f32
+    fn.restype = ci
+    xw, t = np.zeros(96 * 3 * B, dtype=np.float32), _cols(flat, three, flat, two, flat)
+    assert fn(vp(xw.ctypes.data), vp(a.y.ctypes.data), i64(8), i64(12), ci(3), vp(t.ctypes.data), i64(nt), i64(B), vp(0)) == EARG
+    assert b"Not enough decomposition levels" in lib.wx_last_error()
+    assert (a.y == 1).all()
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("fam", FAMS)
 def test_empty_batch_is_ok(wx, fam, dtype):

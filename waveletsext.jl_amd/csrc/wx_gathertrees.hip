@@ -4,8 +4,9 @@
 // "missing" 3).  Here the (ntree, batch) byte matrix goes to the device once and one launch gathers every signal: a workgroup
 // takes a signal, keeps its tree in LDS and every thread walks from the root to the leaf that owns its position -- the depth of
 // that leaf is the column (slice) of the packet table the coefficient comes from.
-// A tree matrix that is in device memory already (bestbasistreeall's own output) is checked there by one launch (wx_trees_prep.hip)
-// and the gather reads the caller's matrix: no staging copy, no host pass.
+// A host matrix is checked by wx_trees_check_host, the column check of every per-signal-tree entry (wx_trees_prep.h).  A tree matrix
+// that is in device memory already (bestbasistreeall's own output) is checked there by one launch (wx_trees_prep) and the gather
+// reads the caller's matrix: no staging copy, no host pass.  Signals and images share one entry, api_trees.
 #include "../../include/waveletsext_hip.h"
 #include "wx_common.h"
 #include "wx_host.h"
@@ -103,40 +104,69 @@ int gt_check_device_trees(bool quad, const uint8_t *trees, int64_t ntree, int64_
     return wx_trees_prep(quad, trees, ntree, batch, k, nullptr, 0, nullptr, nullptr, nullptr, st);
 }
 
+// what api_trees needs to know of a signal of n samples and of an image of m x n: the argument checks of the shape, in its order
+struct GtSignal {
+    int64_t n;
+    static constexpr bool quad = false;
+    bool dims_ok() const { return n >= 1; }
+    int64_t count() const { return n; }
+    int check(int k, int64_t ntree) const
+    {
+        WX_REQUIRE(wx_isdyadic(n), WX_EASSERT, "@assert leaf_len == length(leaf) (Utils.jl:113)");
+        WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
+        WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
+        WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "getbasiscoefall: signal length >= 2^30 not supported");
+        return WX_OK;
+    }
+    int check_host(const uint8_t *trees, int64_t ntree, int64_t batch, int k) const
+    { return wx_trees_check_host(false, n, 1, trees, ntree, batch, k, -1, nullptr, 0, nullptr, nullptr); }
+    template <typename T, bool LDS>
+    void launch(unsigned grid, size_t lds, hipStream_t st, const T *dX, T *dout, int k, int64_t batch, const uint8_t *dt, int ntree) const
+    { hipLaunchKernelGGL((k_gather_trees1d<T, LDS>), dim3(grid), dim3(256), lds, st, dX, dout, (int)n, gt_log2(n), k, batch, dt, ntree); }
+};
+struct GtImage {
+    int64_t m, n;
+    static constexpr bool quad = true;
+    bool dims_ok() const { return m >= 1 && n >= 1; }
+    int64_t count() const { return m * n; }
+    int check(int k, int64_t ntree) const
+    {
+        WX_REQUIRE(k - 1 <= wx_maxtransformlevels(m < n ? m : n), WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
+        WX_REQUIRE(ntree == wx_gettreelength2d(m, n), WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
+        WX_REQUIRE(m < ((int64_t)1 << 20) && n < ((int64_t)1 << 20) && ntree < ((int64_t)1 << 31), WX_EUNSUPPORTED, "getbasiscoefall: image side >= 2^20");
+        return WX_OK;
+    }
+    int check_host(const uint8_t *trees, int64_t ntree, int64_t batch, int k) const
+    { return wx_trees_check_host(true, m, n, trees, ntree, batch, k, -1, nullptr, 0, nullptr, nullptr); }
+    template <typename T, bool LDS>
+    void launch(unsigned grid, size_t lds, hipStream_t st, const T *dX, T *dout, int k, int64_t batch, const uint8_t *dt, int ntree) const
+    { hipLaunchKernelGGL((k_gather_trees2d<T, LDS>), dim3(grid), dim3(256), lds, st, dX, dout, (int)m, (int)n, k, batch, dt, ntree); }
+};
+
 // every tree is checked like the reference does (`@assert all(mapslices(isvalidtree, tree))`, Utils.jl:209) and must not reach below
 // the table (Utils.jl:120, raised by the per-signal getbasiscoef)
-template <typename T>
-int api_trees1d(const T *Xw, T *out, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
+template <typename T, typename S>
+int api_trees(const S &s, const T *Xw, T *out, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
 {
     wx_trees_route_set(WX_TREES_ROUTE_NONE);
-    WX_REQUIRE(n >= 1 && batch >= 0 && k >= 1, WX_EARG, "getbasiscoefall: bad dimensions");
+    WX_REQUIRE(s.dims_ok() && batch >= 0 && k >= 1, WX_EARG, "getbasiscoefall: bad dimensions");
     WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
-    WX_REQUIRE(wx_isdyadic(n), WX_EASSERT, "@assert leaf_len == length(leaf) (Utils.jl:113)");
-    WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
-    WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
-    WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "getbasiscoefall: signal length >= 2^30 not supported");
+    int rc;
+    if ((rc = s.check(k, ntree))) return rc;
     const bool dev_trees = batch > 0 && wx_is_device_ptr(trees);
     hipStream_t st = wx_stream(stream);
-    int rc;
-    if (dev_trees) {
-        if ((rc = gt_check_device_trees(false, trees, ntree, batch, k, st))) return rc;
-    } else
-        for (int64_t b = 0; b < batch; ++b) {
-            const uint8_t *t = trees + b * ntree;
-            WX_REQUIRE(wx_isvalidtree1d(n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-            WX_REQUIRE(wx_tree_depth1d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
-        }
+    if ((rc = dev_trees ? gt_check_device_trees(S::quad, trees, ntree, batch, k, st) : s.check_host(trees, ntree, batch, k))) return rc;
     if ((rc = gt_need_device())) return rc;
     if (batch == 0) return WX_OK;
     WxScratch scr(st);
     const uint8_t *dt = trees;                                         // device trees are read where they are
     if (!dev_trees && !(dt = (const uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch))) return WX_EHIP;
     WxIO io(st);
-    const T *dX = (const T *)io.in(Xw, sizeof(T) * n * k * batch);
-    T *dout = (T *)io.out(out, sizeof(T) * n * batch);
+    const T *dX = (const T *)io.in(Xw, sizeof(T) * s.count() * k * batch);
+    T *dout = (T *)io.out(out, sizeof(T) * s.count() * batch);
     if (!dX || !dout) return io.finish(WX_EHIP);
     // the tree matrix goes over from the caller's (pageable) memory: every return behind this copy waits for the stream first, so the
-    // matrix may be released on return whatever the outcome (ADVICE r5)
+    // matrix may be released on return whatever the outcome
     if (ntree > 0 && !dev_trees) {
         hipError_t e = hipMemcpyAsync(const_cast<uint8_t *>(dt), trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
         if (e != hipSuccess) {
@@ -145,71 +175,10 @@ int api_trees1d(const T *Xw, T *out, int64_t n, int k, const uint8_t *trees, int
         }
     }
     const unsigned grid = (unsigned)(batch < 65536 * 4 ? batch : 65536 * 4);
-    if (ntree <= GT_LDS_MAX)
-        hipLaunchKernelGGL((k_gather_trees1d<T, true>), dim3(grid), dim3(256), (size_t)ntree + 16, st, dX, dout, (int)n, gt_log2(n), k, batch,
-                           dt, (int)ntree);
-    else
-        hipLaunchKernelGGL((k_gather_trees1d<T, false>), dim3(grid), dim3(256), 0, st, dX, dout, (int)n, gt_log2(n), k, batch,
-                           dt, (int)ntree);
+    if (ntree <= GT_LDS_MAX) s.template launch<T, true>(grid, (size_t)ntree + 16, st, dX, dout, k, batch, dt, (int)ntree);
+    else s.template launch<T, false>(grid, 0, st, dX, dout, k, batch, dt, (int)ntree);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess && !dev_trees) e = hipStreamSynchronize(st);   // the host tree matrix may be released on return
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "getbasiscoefall launch", __FILE__, __LINE__));
-    }
-    rc = io.finish(WX_OK);
-    if (rc == WX_OK) wx_trees_route_set(dev_trees ? WX_TREES_ROUTE_DEV_GATHER : WX_TREES_ROUTE_HOST);
-    return rc;
-}
-
-template <typename T>
-int api_trees2d(const T *Xw, T *out, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
-{
-    wx_trees_route_set(WX_TREES_ROUTE_NONE);
-    WX_REQUIRE(m >= 1 && n >= 1 && batch >= 0 && k >= 1, WX_EARG, "getbasiscoefall: bad dimensions");
-    WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
-    const int Lmax = wx_maxtransformlevels(m < n ? m : n);
-    WX_REQUIRE(k - 1 <= Lmax, WX_EASSERT, "@assert k-1 <= maxtransformlevels(x) (Utils.jl:208)");
-    WX_REQUIRE(ntree == wx_gettreelength2d(m, n), WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
-    WX_REQUIRE(m < ((int64_t)1 << 20) && n < ((int64_t)1 << 20) && ntree < ((int64_t)1 << 31), WX_EUNSUPPORTED, "getbasiscoefall: image side >= 2^20");
-    const bool dev_trees = batch > 0 && wx_is_device_ptr(trees);
-    hipStream_t st = wx_stream(stream);
-    int rc;
-    if (dev_trees) {
-        if ((rc = gt_check_device_trees(true, trees, ntree, batch, k, st))) return rc;
-    } else
-        for (int64_t b = 0; b < batch; ++b) {
-            const uint8_t *t = trees + b * ntree;
-            WX_REQUIRE(wx_isvalidtree2d(m, n, t, ntree), WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-            WX_REQUIRE(wx_tree_depth2d(t, ntree) < k, WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
-        }
-    if ((rc = gt_need_device())) return rc;
-    if (batch == 0) return WX_OK;
-    WxScratch scr(st);
-    const uint8_t *dt = trees;                                         // device trees are read where they are
-    if (!dev_trees && !(dt = (const uint8_t *)scr.alloc((size_t)(ntree > 0 ? ntree : 1) * batch))) return WX_EHIP;
-    WxIO io(st);
-    const T *dX = (const T *)io.in(Xw, sizeof(T) * m * n * k * batch);
-    T *dout = (T *)io.out(out, sizeof(T) * m * n * batch);
-    if (!dX || !dout) return io.finish(WX_EHIP);
-    // the tree matrix goes over from the caller's (pageable) memory: every return behind this copy waits for the stream first, so the
-    // matrix may be released on return whatever the outcome (ADVICE r5)
-    if (ntree > 0 && !dev_trees) {
-        hipError_t e = hipMemcpyAsync(const_cast<uint8_t *>(dt), trees, (size_t)ntree * batch, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(st);
-            return io.finish(wx_set_hip_error(e, "getbasiscoefall: tree upload", __FILE__, __LINE__));
-        }
-    }
-    const unsigned grid = (unsigned)(batch < 65536 * 4 ? batch : 65536 * 4);
-    if (ntree <= GT_LDS_MAX)
-        hipLaunchKernelGGL((k_gather_trees2d<T, true>), dim3(grid), dim3(256), (size_t)ntree + 16, st, dX, dout, (int)m, (int)n, k, batch,
-                           dt, (int)ntree);
-    else
-        hipLaunchKernelGGL((k_gather_trees2d<T, false>), dim3(grid), dim3(256), 0, st, dX, dout, (int)m, (int)n, k, batch,
-                           dt, (int)ntree);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess && !dev_trees) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return io.finish(wx_set_hip_error(e, "getbasiscoefall launch", __FILE__, __LINE__));
@@ -224,14 +193,14 @@ int api_trees2d(const T *Xw, T *out, int64_t m, int64_t n, int k, const uint8_t 
 extern "C" {
 
 int wx_getbasiscoef1d_trees_f64(const double *Xw, double *out, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
-{ return api_trees1d<double>(Xw, out, n, k, trees, ntree, batch, stream); }
+{ return api_trees(GtSignal{n}, Xw, out, k, trees, ntree, batch, stream); }
 int wx_getbasiscoef1d_trees_f32(const float *Xw, float *out, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, void *stream)
-{ return api_trees1d<float>(Xw, out, n, k, trees, ntree, batch, stream); }
+{ return api_trees(GtSignal{n}, Xw, out, k, trees, ntree, batch, stream); }
 int wx_getbasiscoef2d_trees_f64(const double *Xw, double *out, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                                 void *stream)
-{ return api_trees2d<double>(Xw, out, m, n, k, trees, ntree, batch, stream); }
+{ return api_trees(GtImage{m, n}, Xw, out, k, trees, ntree, batch, stream); }
 int wx_getbasiscoef2d_trees_f32(const float *Xw, float *out, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                                 void *stream)
-{ return api_trees2d<float>(Xw, out, m, n, k, trees, ntree, batch, stream); }
+{ return api_trees(GtImage{m, n}, Xw, out, k, trees, ntree, batch, stream); }
 
 }  // extern "C"

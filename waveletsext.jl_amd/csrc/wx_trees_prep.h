@@ -23,3 +23,12 @@ void wx_trees_route_set(int route);
 // Returns WX_OK, the two codes above (message set) or WX_EHIP.  ntree == 0: nothing to check, *same = true.
 int wx_trees_prep(bool quad, const uint8_t *trees, int64_t ntree, int64_t batch, int k, uint32_t *bits, int nw, uint8_t *depths,
                   uint8_t *col0, bool *same, hipStream_t st);
+
+// The same for a matrix in HOST memory, in one pass over its columns (wx_isvalidtree*, wx_tree_depth*; m = the signal length or
+// the image's rows, n = its columns, read for quad trees only); a matrix of 2^22 bytes and more is shared by up to 8 threads, a
+// contiguous range of columns each.  max_depth >= 0: no tree is deeper than it, else WX_EASSERT with the message of the sides
+// (images pass the levels both sides divide by); as above, the lowest offending column decides, and it is counted once: as
+// invalid, else as deeper than the sides, else as too deep for k.  `bits` is zero on entry and written for the columns that passed;
+// `same` needs no col0, the caller has the matrix.  Needs no device.
+int wx_trees_check_host(bool quad, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, int k, int max_depth,
+                        uint32_t *bits, int nw, uint8_t *depths, bool *same);

@@ -1,8 +1,8 @@
-// wx_trees_prep.hip -- per-signal trees that stay on the device.  bestbasistreeall(X, BB()) selects every signal's tree on the GPU
-// (wx_treeselect_batch_*, an (ntree, batch) byte matrix); its consumers -- wptall / iwptall / iwpdall with one tree per signal
-// (wx_wpt_trees.hip) and getbasiscoefall (wx_gathertrees.hip) -- took that matrix from host memory, where one pass checked every
-// column (wx_isvalidtree*, wx_tree_depth*), compared it with column 0 and packed it into bits.  k_trees_prep is that pass as one
-// launch over the device matrix; only a record of three words comes back to the host.
+// wx_trees_prep.hip -- the check of a matrix of per-signal trees, for every consumer: wptall / iwptall / iwpdall with one tree per
+// signal or image (wx_trees_host.h) and getbasiscoefall (wx_gathertrees.hip).  One pass checks every column (wx_isvalidtree*,
+// wx_tree_depth*), compares it with column 0 and packs it into bits: wx_trees_check_host for a matrix in host memory, and
+// k_trees_prep, the same pass as one launch, for one that stays on the device -- bestbasistreeall(X, BB()) selects every signal's
+// tree on the GPU (wx_treeselect_batch_*, an (ntree, batch) byte matrix) --, from which only a record of three words comes back.
 //
 // A wavefront walks a column 64 nodes at a time: lane l of step s holds node 64 s + l + 1, and the ballot of "decomposed" IS
 // words 2 s and 2 s + 1 of the column's bit layout (wx_tree_bits.h).  The parent of a node (c >> 1, quad trees (c + 2) >> 2) lies
@@ -17,6 +17,8 @@
 #include "wx_host.h"
 #include "wx_tree_bits.h"
 #include "wx_trees_prep.h"
+#include <thread>
+#include <vector>
 
 namespace {
 
@@ -121,6 +123,50 @@ int wx_trees_prep(bool quad, const uint8_t *trees, int64_t ntree, int64_t batch,
     if (host[REC_INVALID] < host[REC_DEEP]) return wx_set_error(WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
     if (host[REC_DEEP] != ~0ULL) return wx_set_error(WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
     if (same) *same = host[REC_SAME] != 0;
+    return WX_OK;
+}
+
+int wx_trees_check_host(bool quad, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, int k, int max_depth,
+                        uint32_t *bits, int nw, uint8_t *depths, bool *same)
+{
+    enum { BAD_TREE = 1, BAD_SIDES = 2, BAD_K = 3 };
+    struct Part { int code = 0; bool same = true; };                   // of a range of columns: its first error, all equal to column 0
+    auto check = [&](int64_t b0, int64_t b1, Part *out) {
+        for (int64_t b = b0; b < b1; ++b) {
+            const uint8_t *t = trees + b * ntree;
+            int code = 0;
+            if (!(quad ? wx_isvalidtree2d(m, n, t, ntree) : wx_isvalidtree1d(m, t, ntree))) code = BAD_TREE;
+            else {
+                const int depth = quad ? wx_tree_depth2d(t, ntree) : wx_tree_depth1d(t, ntree);
+                if (depths) depths[b] = (uint8_t)depth;
+                if (max_depth >= 0 && depth > max_depth) code = BAD_SIDES;
+                else if (k > 0 && depth >= k) code = BAD_K;
+            }
+            if (code) { out->code = code; return; }
+            if (same && out->same && ntree > 0) out->same = memcmp(trees, t, (size_t)ntree) == 0;
+            if (bits) wt_pack_host(t, ntree, bits + (size_t)b * nw);
+        }
+    };
+    unsigned nth = 1;
+    if (batch * ntree >= ((int64_t)1 << 22)) {
+        nth = std::thread::hardware_concurrency();
+        nth = nth < 1 ? 1 : (nth > 8 ? 8 : nth);
+    }
+    std::vector<Part> parts(nth);
+    if (nth == 1) check(0, batch, &parts[0]);
+    else {
+        std::vector<std::thread> pool;
+        for (unsigned i = 0; i < nth; ++i) pool.emplace_back(check, batch * i / nth, batch * (i + 1) / nth, &parts[i]);
+        for (auto &th : pool) th.join();
+    }
+    bool all_same = true;
+    for (const Part &pt : parts) {                                      // in column order
+        if (pt.code == BAD_TREE) return wx_set_error(WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
+        if (pt.code == BAD_SIDES) return wx_set_error(WX_EASSERT, "both sides must be divisible by 2^depth(tree) (dwt_step! size asserts)");
+        if (pt.code) return wx_set_error(WX_EARG, "Not enough decomposition levels in Xw (Utils.jl:120)");
+        all_same = all_same && pt.same;
+    }
+    if (same) *same = all_same;
     return WX_OK;
 }
 

@@ -15,31 +15,18 @@
 //             into both buffers, so a leaf is found in whichever buffer its sibling was rebuilt into; the root's pass writes HBM.
 //   iwpd      the inverse kernel whose loads take every position from the column of its leaf's depth in the packet table
 //             (getbasiscoef, Utils.jl:101-134).
-// The host checks every tree (a few threads for a large matrix), notes its depth and packs it into bits in the same pass: the kernel
-// gets n / 8 bytes of tree per signal instead of n - 1.  A tree matrix in DEVICE memory (bestbasistreeall's own output) gets the
-// same pass as one launch (wx_trees_prep.hip) and never visits the host inside the window.
+// The kernel gets the trees as bits, n / 8 bytes per signal instead of n - 1, and one depth byte per signal.
 // The filter length is a loop bound: six kernels in all (3 directions x 2 types), the arithmetic is Float64 for either type like the
 // one-level kernels of wx_dwt1d.hip.  No atomics; every output element is written by exactly one lane.
-// Window: what wx_fused1d_ok admits (dyadic 8 <= n <= 8192 Float64 / 16384 Float32, even filters of 2 .. 20 taps).  Outside it the
-// entry calls the single-tree entry once per signal (slow, correct).  Byte-identical columns go to the single-tree entry whole.
-#include "../../include/waveletsext_hip.h"
-#include "wx_common.h"
-#include "wx_host.h"
+// Window: what wx_fused1d_ok admits (dyadic 8 <= n <= 8192 Float64 / 16384 Float32, even filters of 2 .. 20 taps).
+// This file holds the kernel and WtShape, what the host driver needs to know of a signal; the driver itself -- argument checks, the
+// check and packing of the trees on the host or the device, the routes around the window, staging and waits -- is wx_trees_host.h.
 #include "wx_kernels.h"
-#include "wx_tree_bits.h"
-#include "wx_trees_prep.h"
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define WX_REQUIRE(cond, code, msg) \
-    do { if (!(cond)) return wx_set_error(code, msg); } while (0)
-
-extern "C" int wx_device_count(void);
+#include "wx_trees_host.h"
 
 namespace {
 
-enum { WT_FWD = 0, WT_INV = 1, WT_IWPD = 2 };
+enum { WT_FWD = WX_TREES_FWD, WT_INV = WX_TREES_INV, WT_IWPD = WX_TREES_IWPD };
 
 // the tree of a signal as bits: wt_words, wt_set (wx_tree_bits.h)
 
@@ -156,220 +143,53 @@ __global__ __launch_bounds__(1024) void k_wpt_trees(const T *__restrict__ x, T *
     }
 }
 
-template <typename T> size_t wt_lds_bytes(int64_t n) { return sizeof(double) * WX_MAXF + (size_t)2 * n * sizeof(T) + sizeof(uint32_t) * wt_words(n); }
-
-// one lane per output pair of a level, at most 1024
-int wt_threads(int64_t n)
-{
-    int nt = 64;
-    while (nt < 1024 && nt < n / 2) nt <<= 1;
-    return nt;
-}
-
-// workgroups resident on the 256 CUs (160 KiB of LDS and 2048 lanes each, at most 16 workgroups), never more than signals
-int wt_grid(size_t lds, int nt, int64_t batch)
-{
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 2048 / nt) per_cu = 2048 / nt;
-    if (per_cu > 16) per_cu = 16;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t g = (int64_t)256 * per_cu;
-    return (int)(g < batch ? g : batch);
-}
-
-int wt_single(const double *x, double *y, int64_t n, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st, int mode)
-{
-    if (mode == WT_FWD) return wx_wpt1d_f64(x, y, n, 0, t, nt, batch, qmf, F, st);
-    if (mode == WT_INV) return wx_iwpt1d_f64(x, y, n, 0, t, nt, batch, qmf, F, st);
-    return wx_iwpd1d_f64(x, y, n, k, 0, t, nt, batch, qmf, F, st);
-}
-int wt_single(const float *x, float *y, int64_t n, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st, int mode)
-{
-    if (mode == WT_FWD) return wx_wpt1d_f32(x, y, n, 0, t, nt, batch, qmf, F, st);
-    if (mode == WT_INV) return wx_iwpt1d_f32(x, y, n, 0, t, nt, batch, qmf, F, st);
-    return wx_iwpd1d_f32(x, y, n, k, 0, t, nt, batch, qmf, F, st);
-}
-
-template <typename T> bool wt_lds_path(int64_t n, int F) { return wx_fused1d_ok<T>(n, F) && wt_lds_bytes<T>(n) <= 160 * 1024; }
-
-// the launch of k_wpt_trees: dt = the trees' bits, dd = one depth byte per signal, both in device memory
-template <typename T, int MODE>
-hipError_t wt_launch(const T *dx, T *dy, int64_t n, int k, int64_t batch, const uint32_t *dt, const uint8_t *dd, const WxFilt &filt,
-                     hipStream_t st)
-{
-    const size_t lds = wt_lds_bytes<T>(n);
-    const int nt = wt_threads(n);
-    auto kern = k_wpt_trees<T, MODE>;
-    hipError_t e = hipSuccess;
-    if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    int log2n = 0;
-    while (((int64_t)1 << log2n) < n) ++log2n;
-    hipLaunchKernelGGL(kern, dim3(wt_grid(lds, nt, batch)), dim3(nt), lds, st, dx, dy, log2n, k, batch, dt, dd, filt);
-    return hipGetLastError();
-}
-
-template <typename T, int MODE>
-int wt_host_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                  void *stream, const WxFilt &filt);
-
-// trees in device memory (batch > 0, the argument checks that need no tree content are done): see include/waveletsext_hip.h
-template <typename T, int MODE>
-int wt_device_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                    void *stream, const WxFilt &filt)
-{
-    WX_REQUIRE(!wx_on_other_device(trees), WX_EARG, "tree matrix lives on another device than the current one");
-    hipStream_t st = wx_stream(stream);
-    if (!wt_lds_path<T>(n, F)) {
-        // outside the LDS kernel's window: the matrix comes to the host once and the host path runs (correct and slow)
-        std::vector<uint8_t> ht((size_t)(ntree > 0 ? ntree * batch : 1));
-        if (ntree > 0) {
-            hipError_t e = hipMemcpyAsync(ht.data(), trees, (size_t)ntree * batch, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(st);
-                return wx_set_hip_error(e, "wptall(trees): tree matrix to the host", __FILE__, __LINE__);
-            }
-        }
-        const int rc = wt_host_trees<T, MODE>(x, y, n, k, ht.data(), ntree, batch, qmf, F, stream, filt);
-        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_COPIED);
-        return rc;
-    }
-    const int nw = wt_words(n);
-    WxScratch scr(st);
-    const size_t tbytes = sizeof(uint32_t) * nw * (size_t)batch;
-    uint8_t *dt = (uint8_t *)scr.alloc(tbytes + (size_t)batch);         // the trees' bits, then one depth byte per signal
-    if (!dt) return WX_EHIP;
-    uint8_t *dd = dt + tbytes;
-    std::vector<uint8_t> col0((size_t)ntree);
-    bool same = true;
-    int rc = wx_trees_prep(false, trees, ntree, batch, MODE == WT_IWPD ? k : 0, (uint32_t *)dt, nw, dd, col0.data(), &same, st);
-    if (rc) return rc;                                                 // nothing has been written to y
-    if (same) {                                                        // one tree after all: as the host path does, with the same result
-        rc = wt_single(x, y, n, k, col0.data(), ntree, batch, qmf, F, stream, MODE);
-        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_SINGLE);
-        return rc;
-    }
-    WxIO io(st);
-    const T *dx = (const T *)io.in(x, sizeof(T) * n * (MODE == WT_IWPD ? k : 1) * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * n * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
-    const hipError_t e = wt_launch<T, MODE>(dx, dy, n, k, batch, (const uint32_t *)dt, dd, filt, st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees) launch", __FILE__, __LINE__));
-    }
-    rc = io.finish(WX_OK);                                             // device arrays: nothing waits, the scratch is freed in stream order
-    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_LDS);
-    return rc;
-}
-
-template <typename T, int MODE>
-int api_wpt_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                  void *stream)
-{
-    wx_trees_route_set(WX_TREES_ROUTE_NONE);
-    WxFilt filt;
-    int rc = wx_pack_filter(qmf, F, &filt);
-    if (rc) return rc;
-    // argument errors are reported before any device is needed, with the codes of the single-tree entries and of getbasiscoefall
-    WX_REQUIRE(n >= 1 && batch >= 0 && k >= 1, WX_EARG, "wptall(trees): bad dimensions");
-    WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
-    WX_REQUIRE(batch == 0 || (const void *)x != (const void *)y, WX_EARG, "wptall(trees): input and output must not be the same array");
-    WX_REQUIRE(wx_isdyadic(n), WX_EASSERT, "maketree/isvalidtree: signal length must be dyadic (Wavelets.jl)");
-    if (MODE == WT_IWPD) WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "getbasiscoef: @assert k-1 <= L (Utils.jl:110)");
-    WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
-    WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "wptall(trees): signal length >= 2^30 not supported");
-    if (batch > 0 && wx_is_device_ptr(trees)) return wt_device_trees<T, MODE>(x, y, n, k, trees, ntree, batch, qmf, F, stream, filt);
-    rc = wt_host_trees<T, MODE>(x, y, n, k, trees, ntree, batch, qmf, F, stream, filt);
-    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_HOST);
-    return rc;
-}
-
-// trees in host memory
-template <typename T, int MODE>
-int wt_host_trees(const T *x, T *y, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                  void *stream, const WxFilt &filt)
-{
-    int rc;
-    // every tree is checked like the reference does (Utils.jl:209), and for iwpd must not reach below the table (Utils.jl:120); the
-    // first offending column decides the error.  A large matrix is checked by a few host threads, a range of columns each.
-    // The LDS kernel takes the trees as bits (an eighth of the bytes to upload), packed by the same pass.
-    const bool lds_path = wt_lds_path<T>(n, F);
-    const int nw = wt_words(n);
-    std::vector<uint8_t> depths((size_t)(batch > 0 ? batch : 1));
-    std::vector<uint32_t> bits(lds_path ? (size_t)nw * batch : 0);
-    struct Part { int code = WX_OK; bool same = true; };               // of a range of columns: its first error, all equal to column 0
-    auto check = [&](int64_t b0, int64_t b1, Part *out) {
-        for (int64_t b = b0; b < b1; ++b) {
-            const uint8_t *t = trees + b * ntree;
-            int code = WX_OK;
-            if (!wx_isvalidtree1d(n, t, ntree)) code = WX_EASSERT;
-            else {
-                const int depth = wx_tree_depth1d(t, ntree);
-                depths[(size_t)b] = (uint8_t)depth;
-                if (MODE == WT_IWPD && depth >= k) code = WX_EARG;
-            }
-            if (code) { out->code = code; return; }
-            if (out->same && ntree > 0) out->same = memcmp(trees, t, (size_t)ntree) == 0;
-            if (lds_path) wt_pack_host(t, ntree, bits.data() + (size_t)b * nw);    // zero-initialised
-        }
-    };
-    unsigned nth = 1;
-    if (batch * ntree >= ((int64_t)1 << 22)) {
-        nth = std::thread::hardware_concurrency();
-        nth = nth < 1 ? 1 : (nth > 8 ? 8 : nth);
-    }
-    std::vector<Part> parts(nth);
-    if (nth == 1) check(0, batch, &parts[0]);
-    else {
-        std::vector<std::thread> pool;
-        for (unsigned i = 0; i < nth; ++i) pool.emplace_back(check, batch * i / nth, batch * (i + 1) / nth, &parts[i]);
-        for (auto &th : pool) th.join();
-    }
-    bool same = true;
-    for (const Part &pt : parts) {                                      // in column order
-        if (pt.code == WX_EASSERT) return wx_set_error(WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-        if (pt.code) return wx_set_error(WX_EARG, "getbasiscoef: Not enough decomposition levels in Xw (Utils.jl:120)");
-        same = same && pt.same;
-    }
-    if (batch == 0) return WX_OK;
-    if (wx_device_count() < 1) return wx_set_error(WX_EHIP, "no HIP device visible: the MI355X kernels cannot run");
-    // one tree after all: the single-tree entry has the lattice kernels
-    if (same) return wt_single(x, y, n, k, trees, ntree, batch, qmf, F, stream, MODE);
-    // outside the LDS kernel's window: the single-tree path once per signal.  Slow (a tree upload and a launch sequence per signal).
-    if (!lds_path) {
-        const int64_t xs = MODE == WT_IWPD ? n * (int64_t)k : n;
-        for (int64_t b = 0; b < batch; ++b)
-            if ((rc = wt_single(x + b * xs, y + b * n, n, k, trees + b * ntree, ntree, 1, qmf, F, stream, MODE))) return rc;
+// what the driver (wx_trees_host.h) needs to know of a signal of n samples
+struct WtShape {
+    int64_t n;
+    static constexpr bool quad = false;
+    bool dims_ok() const { return n >= 1; }
+    int64_t count() const { return n; }
+    int check(bool iwpd, int k, int64_t ntree) const
+    {
+        WX_REQUIRE(wx_isdyadic(n), WX_EASSERT, "maketree/isvalidtree: signal length must be dyadic (Wavelets.jl)");
+        if (iwpd) WX_REQUIRE(k - 1 <= wx_maxtransformlevels(n), WX_EASSERT, "getbasiscoef: @assert k-1 <= L (Utils.jl:110)");
+        WX_REQUIRE(ntree == n - 1, WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
+        WX_REQUIRE(n < ((int64_t)1 << 30), WX_EUNSUPPORTED, "wptall(trees): signal length >= 2^30 not supported");
         return WX_OK;
     }
-    hipStream_t st = wx_stream(stream);
-    WxScratch scr(st);
-    const size_t tbytes = sizeof(uint32_t) * nw * (size_t)batch;
-    uint8_t *dt = (uint8_t *)scr.alloc(tbytes + (size_t)batch);         // the trees' bits, then one depth byte per signal
-    if (!dt) return WX_EHIP;
-    uint8_t *dd = dt + tbytes;
-    WxIO io(st);
-    const T *dx = (const T *)io.in(x, sizeof(T) * n * (MODE == WT_IWPD ? k : 1) * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * n * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
-    // the packed trees go over from pageable memory of this call: every return behind these copies waits for the stream first.  (The
-    // caller's matrix is not read past this point: it may be released on return, as with wx_getbasiscoef1d_trees_*.)
-    hipError_t e = hipMemcpyAsync(dt, bits.data(), tbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dd, depths.data(), (size_t)batch, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees): tree upload", __FILE__, __LINE__));
+    int check_host(const uint8_t *trees, int64_t ntree, int64_t batch, int k, uint32_t *bits, int nw, uint8_t *depths, bool *same) const
+    { return wx_trees_check_host(false, n, 1, trees, ntree, batch, k, -1, bits, nw, depths, same); }
+    // WX_MAXF doubles | two buffers of n elements | the tree's words: wt_words(n), which is wq_words(n - 1) for every dyadic n
+    template <typename T> size_t lds() const { return sizeof(double) * WX_MAXF + (size_t)2 * n * sizeof(T) + sizeof(uint32_t) * wt_words(n); }
+    template <typename T> bool window(int64_t, int F) const { return wx_fused1d_ok<T>(n, F) && lds<T>() <= 160 * 1024; }
+    int single(int mode, const double *x, double *y, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st) const
+    {
+        if (mode == WT_FWD) return wx_wpt1d_f64(x, y, n, 0, t, nt, batch, qmf, F, st);
+        if (mode == WT_INV) return wx_iwpt1d_f64(x, y, n, 0, t, nt, batch, qmf, F, st);
+        return wx_iwpd1d_f64(x, y, n, k, 0, t, nt, batch, qmf, F, st);
     }
-    e = wt_launch<T, MODE>(dx, dy, n, k, batch, (const uint32_t *)dt, dd, filt, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                 // `bits` and `depths` are released on return
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees) launch", __FILE__, __LINE__));
+    int single(int mode, const float *x, float *y, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st) const
+    {
+        if (mode == WT_FWD) return wx_wpt1d_f32(x, y, n, 0, t, nt, batch, qmf, F, st);
+        if (mode == WT_INV) return wx_iwpt1d_f32(x, y, n, 0, t, nt, batch, qmf, F, st);
+        return wx_iwpd1d_f32(x, y, n, k, 0, t, nt, batch, qmf, F, st);
     }
-    return io.finish(WX_OK);
-}
+    template <typename T, int MODE>
+    hipError_t launch(const T *dx, T *dy, int64_t, int k, int64_t batch, const uint32_t *dt, const uint8_t *dd, const WxFilt &filt,
+                      hipStream_t st) const
+    {
+        const size_t bytes = lds<T>();
+        const int nt = wx_trees_threads(n);
+        auto kern = k_wpt_trees<T, MODE>;
+        hipError_t e = hipSuccess;
+        if (bytes > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        int log2n = 0;
+        while (((int64_t)1 << log2n) < n) ++log2n;
+        hipLaunchKernelGGL(kern, dim3(wx_trees_grid(bytes, nt, batch)), dim3(nt), bytes, st, dx, dy, log2n, k, batch, dt, dd, filt);
+        return hipGetLastError();
+    }
+};
 
 }  // namespace
 
@@ -377,21 +197,21 @@ extern "C" {
 
 int wx_wpt1d_trees_f64(const double *x, double *y, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
                        void *stream)
-{ return api_wpt_trees<double, WT_FWD>(x, y, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WT_FWD>(WtShape{n}, x, y, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_wpt1d_trees_f32(const float *x, float *y, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
                        void *stream)
-{ return api_wpt_trees<float, WT_FWD>(x, y, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WT_FWD>(WtShape{n}, x, y, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpt1d_trees_f64(const double *xw, double *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
                         int F, void *stream)
-{ return api_wpt_trees<double, WT_INV>(xw, xhat, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WT_INV>(WtShape{n}, xw, xhat, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpt1d_trees_f32(const float *xw, float *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
                         int F, void *stream)
-{ return api_wpt_trees<float, WT_INV>(xw, xhat, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WT_INV>(WtShape{n}, xw, xhat, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpd1d_trees_f64(const double *xw, double *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees<double, WT_IWPD>(xw, xhat, n, k, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WT_IWPD>(WtShape{n}, xw, xhat, k, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpd1d_trees_f32(const float *xw, float *xhat, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees<float, WT_IWPD>(xw, xhat, n, k, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WT_IWPD>(WtShape{n}, xw, xhat, k, trees, ntree, batch, qmf, F, stream); }
 
 }  // extern "C"

@@ -23,31 +23,16 @@
 // loop bound, two taps per turn, the taps scalar loads from the kernel arguments (no LDS traffic for them): six kernels in all
 // (3 directions x 2 types); the arithmetic is Float64 for either type.  No atomics; every output
 // element is written by exactly one lane.
-// The host checks every tree, notes its depth and packs it into bits in the same pass (wx_tree_bits.h: node i is bit i - 1, heap
-// order); a tree matrix in DEVICE memory gets the same pass as one launch (wx_trees_prep.hip, quad form).
+// The kernel gets the trees as bits (wx_tree_bits.h: node i is bit i - 1, heap order) and one depth byte per image.
 // Window: both sides dyadic and >= 8, m n <= 8192 (Float64) / 16384 (Float32) -- two buffers and the tree's bits are at
-// most 129 of the 160 KiB --, even filters of 2 .. 20 taps.  Outside it the entry calls the single-tree entry once per image (slow,
-// correct).  Byte-identical columns go to the single-tree entry whole.
-#include "../../include/waveletsext_hip.h"
-#include "wx_common.h"
-#include "wx_host.h"
-#include "wx_tree_bits.h"
-#include "wx_trees_prep.h"
-#include <cstring>
-#include <thread>
-#include <vector>
-
-#define WX_REQUIRE(cond, code, msg) \
-    do { if (!(cond)) return wx_set_error(code, msg); } while (0)
-
-extern "C" int wx_device_count(void);
+// most 129 of the 160 KiB --, even filters of 2 .. 20 taps.
+// This file holds the kernel and WqShape, what the host driver needs to know of an image; the driver itself is wx_trees_host.h,
+// shared with wx_wpt_trees.hip.
+#include "wx_trees_host.h"
 
 namespace {
 
-enum { WQ_FWD = 0, WQ_INV = 1, WQ_IWPD = 2 };
-
-// words of tree bits per image (at least one)
-__host__ __device__ __forceinline__ int wq_words(int64_t ntree) { return ntree > 32 ? (int)((ntree + 31) >> 5) : 1; }
+enum { WQ_FWD = WX_TREES_FWD, WQ_INV = WX_TREES_INV, WQ_IWPD = WX_TREES_IWPD };
 
 // the bits of v (< 256) at the even positions
 __device__ __forceinline__ int wq_spread(int v)
@@ -226,239 +211,64 @@ __global__ __launch_bounds__(1024) void k_wpt_trees2d(const T *__restrict__ x, T
     }
 }
 
-template <typename T> size_t wq_lds_bytes(int64_t mn, int64_t ntree) { return (size_t)2 * mn * sizeof(T) + sizeof(uint32_t) * wq_words(ntree); }
-
-// the window of one launch
-template <typename T> bool wq_lds_path(int64_t m, int64_t n, int64_t ntree, int F)
-{
-    if (!wx_isdyadic(m) || !wx_isdyadic(n) || m < 8 || n < 8) return false;
-    if (m * n > (sizeof(T) == 8 ? 8192 : 16384)) return false;
-    if (F < 2 || F > 20 || (F & 1)) return false;
-    return wq_lds_bytes<T>(m * n, ntree) <= 160 * 1024;
-}
-
-// one lane per output pair of a pass, at most 1024
-int wq_threads(int64_t mn)
-{
-    int nt = 64;
-    while (nt < 1024 && nt < mn / 2) nt <<= 1;
-    return nt;
-}
-
-// workgroups resident on the 256 CUs (160 KiB of LDS and 2048 lanes each, at most 16 workgroups), never more than images
-int wq_grid(size_t lds, int nt, int64_t batch)
-{
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 2048 / nt) per_cu = 2048 / nt;
-    if (per_cu > 16) per_cu = 16;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t g = (int64_t)256 * per_cu;
-    return (int)(g < batch ? g : batch);
-}
-
-int wq_single(const double *x, double *y, int64_t m, int64_t n, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F,
-              void *st, int mode)
-{
-    if (mode == WQ_FWD) return wx_wpt2d_f64(x, y, m, n, 0, t, nt, batch, qmf, F, st);
-    if (mode == WQ_INV) return wx_iwpt2d_f64(x, y, m, n, 0, t, nt, batch, qmf, F, st);
-    return wx_iwpd2d_f64(x, y, m, n, k, 0, t, nt, batch, qmf, F, st);
-}
-int wq_single(const float *x, float *y, int64_t m, int64_t n, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F,
-              void *st, int mode)
-{
-    if (mode == WQ_FWD) return wx_wpt2d_f32(x, y, m, n, 0, t, nt, batch, qmf, F, st);
-    if (mode == WQ_INV) return wx_iwpt2d_f32(x, y, m, n, 0, t, nt, batch, qmf, F, st);
-    return wx_iwpd2d_f32(x, y, m, n, k, 0, t, nt, batch, qmf, F, st);
-}
-
-int wq_log2(int64_t v) { int l = 0; while (v > 1) { v >>= 1; ++l; } return l; }
-
-// the launch of k_wpt_trees2d: dt = the trees' bits, dd = one depth byte per image, both in device memory
-template <typename T, int MODE>
-hipError_t wq_launch(const T *dx, T *dy, int64_t m, int64_t n, int64_t ntree, int k, int64_t batch, const uint32_t *dt, const uint8_t *dd,
-                     const WxFilt &filt, hipStream_t st)
-{
-    const size_t lds = wq_lds_bytes<T>(m * n, ntree);
-    const int nt = wq_threads(m * n);
-    auto kern = k_wpt_trees2d<T, MODE>;
-    hipError_t e = hipSuccess;
-    if (lds > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, dim3(wq_grid(lds, nt, batch)), dim3(nt), lds, st, dx, dy, wq_log2(m), wq_log2(n), (int)ntree, wq_words(ntree), k,
-                       batch, dt, dd, filt);
-    return hipGetLastError();
-}
-
-template <typename T, int MODE>
-int wq_host_trees(const T *x, T *y, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                  void *stream, const WxFilt &filt);
-
-// trees in device memory (batch > 0, the argument checks that need no tree content are done): see include/waveletsext_hip.h
-template <typename T, int MODE>
-int wq_device_trees(const T *x, T *y, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                    void *stream, const WxFilt &filt)
-{
-    WX_REQUIRE(!wx_on_other_device(trees), WX_EARG, "tree matrix lives on another device than the current one");
-    hipStream_t st = wx_stream(stream);
-    if (!wq_lds_path<T>(m, n, ntree, F)) {
-        // outside the LDS kernel's window: the matrix comes to the host once and the host path runs (correct and slow)
-        std::vector<uint8_t> ht((size_t)(ntree > 0 ? ntree * batch : 1));
-        if (ntree > 0) {
-            hipError_t e = hipMemcpyAsync(ht.data(), trees, (size_t)ntree * batch, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                (void)hipStreamSynchronize(st);
-                return wx_set_hip_error(e, "wptall(trees): tree matrix to the host", __FILE__, __LINE__);
-            }
-        }
-        const int rc = wq_host_trees<T, MODE>(x, y, m, n, k, ht.data(), ntree, batch, qmf, F, stream, filt);
-        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_COPIED);
-        return rc;
-    }
-    // inside the window both sides are dyadic: no valid tree is deeper than either side divides by
-    const int nw = wq_words(ntree);
-    const int64_t mn = m * n;
-    WxScratch scr(st);
-    const size_t tbytes = sizeof(uint32_t) * nw * (size_t)batch;
-    uint8_t *dt = (uint8_t *)scr.alloc(tbytes + (size_t)batch);         // the trees' bits, then one depth byte per image
-    if (!dt) return WX_EHIP;
-    uint8_t *dd = dt + tbytes;
-    std::vector<uint8_t> col0((size_t)ntree);
-    bool same = true;
-    int rc = wx_trees_prep(true, trees, ntree, batch, MODE == WQ_IWPD ? k : 0, (uint32_t *)dt, nw, dd, col0.data(), &same, st);
-    if (rc) return rc;                                                 // nothing has been written to y
-    if (same) {                                                        // one tree after all: as the host path does, with the same result
-        rc = wq_single(x, y, m, n, k, col0.data(), ntree, batch, qmf, F, stream, MODE);
-        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_SINGLE);
-        return rc;
-    }
-    WxIO io(st);
-    const T *dx = (const T *)io.in(x, sizeof(T) * mn * (MODE == WQ_IWPD ? k : 1) * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * mn * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
-    const hipError_t e = wq_launch<T, MODE>(dx, dy, m, n, ntree, k, batch, (const uint32_t *)dt, dd, filt, st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees) launch", __FILE__, __LINE__));
-    }
-    rc = io.finish(WX_OK);                                             // device arrays: nothing waits, the scratch is freed in stream order
-    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_LDS);
-    return rc;
-}
-
-template <typename T, int MODE>
-int api_wpt_trees2d(const T *x, T *y, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                    void *stream)
-{
-    wx_trees_route_set(WX_TREES_ROUTE_NONE);
-    WxFilt filt;
-    int rc = wx_pack_filter(qmf, F, &filt);
-    if (rc) return rc;
-    // argument errors are reported before any device is needed, with the codes of the 1-D entries, of the single-tree 2-D entries
-    // (wx_check_tree2d, wx_api_2d.hip) and of getbasiscoefall
-    WX_REQUIRE(m >= 1 && n >= 1 && batch >= 0 && k >= 1, WX_EARG, "wptall(trees): bad dimensions");
-    WX_REQUIRE(batch == 0 || trees != nullptr, WX_EARG, "NULL tree matrix");
-    WX_REQUIRE(batch == 0 || (const void *)x != (const void *)y, WX_EARG, "wptall(trees): input and output must not be the same array");
-    if (MODE == WQ_IWPD)
-        WX_REQUIRE(k - 1 <= wx_maxtransformlevels(m < n ? m : n), WX_EASSERT, "getbasiscoef: @assert k-1 <= maxtransformlevels(x) (Utils.jl:110)");
-    WX_REQUIRE(ntree == wx_gettreelength2d(m, n), WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
-    WX_REQUIRE(m < ((int64_t)1 << 20) && n < ((int64_t)1 << 20) && ntree < ((int64_t)1 << 31), WX_EUNSUPPORTED, "wptall(trees): image side >= 2^20");
-    if (batch > 0 && wx_is_device_ptr(trees)) return wq_device_trees<T, MODE>(x, y, m, n, k, trees, ntree, batch, qmf, F, stream, filt);
-    rc = wq_host_trees<T, MODE>(x, y, m, n, k, trees, ntree, batch, qmf, F, stream, filt);
-    if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_HOST);
-    return rc;
-}
-
-// trees in host memory
-template <typename T, int MODE>
-int wq_host_trees(const T *x, T *y, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf, int F,
-                  void *stream, const WxFilt &filt)
-{
-    int rc;
-    // every tree is checked like the reference does (Utils.jl:209), must not be deeper than both sides divide by (the size asserts of
-    // the 2-D dwt_step!, wx_check_tree2d) and for iwpd must not reach below the table (Utils.jl:120); the first offending column
-    // decides the error.  A large matrix is checked by a few host threads, a range of columns each.
-    // The LDS kernel takes the trees as bits (an eighth of the bytes to upload), packed by the same pass.
-    const bool lds_path = wq_lds_path<T>(m, n, ntree, F);
-    const int nw = wq_words(ntree);
-    const int64_t mn = m * n;
-    const int Lm = wx_maxtransformlevels(m), Ln = wx_maxtransformlevels(n), Lside = Lm < Ln ? Lm : Ln;
-    std::vector<uint8_t> depths((size_t)(batch > 0 ? batch : 1));
-    std::vector<uint32_t> bits(lds_path ? (size_t)nw * batch : 0);
-    enum { BAD_TREE = 1, BAD_SIDES = 2, BAD_K = 3 };
-    struct Part { int code = 0; bool same = true; };                   // of a range of columns: its first error, all equal to column 0
-    auto check = [&](int64_t b0, int64_t b1, Part *out) {
-        for (int64_t b = b0; b < b1; ++b) {
-            const uint8_t *t = trees + b * ntree;
-            int code = 0;
-            if (!wx_isvalidtree2d(m, n, t, ntree)) code = BAD_TREE;
-            else {
-                const int depth = wx_tree_depth2d(t, ntree);
-                depths[(size_t)b] = (uint8_t)depth;
-                if (depth > Lside) code = BAD_SIDES;
-                else if (MODE == WQ_IWPD && depth >= k) code = BAD_K;
-            }
-            if (code) { out->code = code; return; }
-            if (out->same && ntree > 0) out->same = memcmp(trees, t, (size_t)ntree) == 0;
-            if (lds_path) wt_pack_host(t, ntree, bits.data() + (size_t)b * nw);    // zero-initialised
-        }
-    };
-    unsigned nth = 1;
-    if (batch * ntree >= ((int64_t)1 << 22)) {
-        nth = std::thread::hardware_concurrency();
-        nth = nth < 1 ? 1 : (nth > 8 ? 8 : nth);
-    }
-    std::vector<Part> parts(nth);
-    if (nth == 1) check(0, batch, &parts[0]);
-    else {
-        std::vector<std::thread> pool;
-        for (unsigned i = 0; i < nth; ++i) pool.emplace_back(check, batch * i / nth, batch * (i + 1) / nth, &parts[i]);
-        for (auto &th : pool) th.join();
-    }
-    bool same = true;
-    for (const Part &pt : parts) {                                      // in column order
-        if (pt.code == BAD_TREE) return wx_set_error(WX_EASSERT, "@assert all(mapslices(isvalidtree, tree)) (Utils.jl:209)");
-        if (pt.code == BAD_SIDES) return wx_set_error(WX_EASSERT, "both sides must be divisible by 2^depth(tree) (dwt_step! size asserts)");
-        if (pt.code) return wx_set_error(WX_EARG, "getbasiscoef: Not enough decomposition levels in Xw (Utils.jl:120)");
-        same = same && pt.same;
-    }
-    if (batch == 0) return WX_OK;
-    if (wx_device_count() < 1) return wx_set_error(WX_EHIP, "no HIP device visible: the MI355X kernels cannot run");
-    // one tree after all: the single-tree entry has the register kernels of 64 x 64 images
-    if (same) return wq_single(x, y, m, n, k, trees, ntree, batch, qmf, F, stream, MODE);
-    // outside the LDS kernel's window: the single-tree path once per image.  Slow (a tree upload and a launch sequence per image).
-    if (!lds_path) {
-        const int64_t xs = MODE == WQ_IWPD ? mn * (int64_t)k : mn;
-        for (int64_t b = 0; b < batch; ++b)
-            if ((rc = wq_single(x + b * xs, y + b * mn, m, n, k, trees + b * ntree, ntree, 1, qmf, F, stream, MODE))) return rc;
+// what the driver (wx_trees_host.h) needs to know of an image of m x n samples
+struct WqShape {
+    int64_t m, n;
+    static constexpr bool quad = true;
+    bool dims_ok() const { return m >= 1 && n >= 1; }
+    int64_t count() const { return m * n; }
+    // with the codes of the 1-D entries, of the single-tree 2-D entries (wx_check_tree2d, wx_api_2d.hip) and of getbasiscoefall
+    int check(bool iwpd, int k, int64_t ntree) const
+    {
+        if (iwpd)
+            WX_REQUIRE(k - 1 <= wx_maxtransformlevels(m < n ? m : n), WX_EASSERT, "getbasiscoef: @assert k-1 <= maxtransformlevels(x) (Utils.jl:110)");
+        WX_REQUIRE(ntree == wx_gettreelength2d(m, n), WX_EASSERT, "@assert n_t == gettreelength(sz...) (Utils.jl:211)");
+        WX_REQUIRE(m < ((int64_t)1 << 20) && n < ((int64_t)1 << 20) && ntree < ((int64_t)1 << 31), WX_EUNSUPPORTED, "wptall(trees): image side >= 2^20");
         return WX_OK;
     }
-    hipStream_t st = wx_stream(stream);
-    WxScratch scr(st);
-    const size_t tbytes = sizeof(uint32_t) * nw * (size_t)batch;
-    uint8_t *dt = (uint8_t *)scr.alloc(tbytes + (size_t)batch);         // the trees' bits, then one depth byte per image
-    if (!dt) return WX_EHIP;
-    uint8_t *dd = dt + tbytes;
-    WxIO io(st);
-    const T *dx = (const T *)io.in(x, sizeof(T) * mn * (MODE == WQ_IWPD ? k : 1) * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * mn * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
-    // the packed trees go over from pageable memory of this call: every return behind these copies waits for the stream first.  (The
-    // caller's matrix is not read past this point: it may be released on return, as with wx_getbasiscoef2d_trees_*.)
-    hipError_t e = hipMemcpyAsync(dt, bits.data(), tbytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dd, depths.data(), (size_t)batch, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees): tree upload", __FILE__, __LINE__));
+    // no tree may be deeper than both sides divide by
+    int check_host(const uint8_t *trees, int64_t ntree, int64_t batch, int k, uint32_t *bits, int nw, uint8_t *depths, bool *same) const
+    {
+        const int Lm = wx_maxtransformlevels(m), Ln = wx_maxtransformlevels(n);
+        return wx_trees_check_host(true, m, n, trees, ntree, batch, k, Lm < Ln ? Lm : Ln, bits, nw, depths, same);
     }
-    e = wq_launch<T, MODE>(dx, dy, m, n, ntree, k, batch, (const uint32_t *)dt, dd, filt, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);                 // `bits` and `depths` are released on return
-    if (e != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return io.finish(wx_set_hip_error(e, "wptall(trees) launch", __FILE__, __LINE__));
+    // two buffers of m n elements | the tree's words
+    template <typename T> size_t lds(int64_t ntree) const { return (size_t)2 * m * n * sizeof(T) + sizeof(uint32_t) * wq_words(ntree); }
+    // the window of one launch
+    template <typename T> bool window(int64_t ntree, int F) const
+    {
+        if (!wx_isdyadic(m) || !wx_isdyadic(n) || m < 8 || n < 8) return false;
+        if (m * n > (sizeof(T) == 8 ? 8192 : 16384)) return false;
+        if (F < 2 || F > 20 || (F & 1)) return false;
+        return lds<T>(ntree) <= 160 * 1024;
     }
-    return io.finish(WX_OK);
-}
+    int single(int mode, const double *x, double *y, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st) const
+    {
+        if (mode == WQ_FWD) return wx_wpt2d_f64(x, y, m, n, 0, t, nt, batch, qmf, F, st);
+        if (mode == WQ_INV) return wx_iwpt2d_f64(x, y, m, n, 0, t, nt, batch, qmf, F, st);
+        return wx_iwpd2d_f64(x, y, m, n, k, 0, t, nt, batch, qmf, F, st);
+    }
+    int single(int mode, const float *x, float *y, int k, const uint8_t *t, int64_t nt, int64_t batch, const double *qmf, int F, void *st) const
+    {
+        if (mode == WQ_FWD) return wx_wpt2d_f32(x, y, m, n, 0, t, nt, batch, qmf, F, st);
+        if (mode == WQ_INV) return wx_iwpt2d_f32(x, y, m, n, 0, t, nt, batch, qmf, F, st);
+        return wx_iwpd2d_f32(x, y, m, n, k, 0, t, nt, batch, qmf, F, st);
+    }
+    template <typename T, int MODE>
+    hipError_t launch(const T *dx, T *dy, int64_t ntree, int k, int64_t batch, const uint32_t *dt, const uint8_t *dd, const WxFilt &filt,
+                      hipStream_t st) const
+    {
+        const size_t bytes = lds<T>(ntree);
+        const int nt = wx_trees_threads(m * n);
+        auto kern = k_wpt_trees2d<T, MODE>;
+        hipError_t e = hipSuccess;
+        if (bytes > 64 * 1024) e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(wx_trees_grid(bytes, nt, batch)), dim3(nt), bytes, st, dx, dy, wx_maxtransformlevels(m),
+                           wx_maxtransformlevels(n), (int)ntree, wq_words(ntree), k, batch, dt, dd, filt);
+        return hipGetLastError();
+    }
+};
 
 }  // namespace
 
@@ -466,21 +276,21 @@ extern "C" {
 
 int wx_wpt2d_trees_f64(const double *x, double *y, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
                        int F, void *stream)
-{ return api_wpt_trees2d<double, WQ_FWD>(x, y, m, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WQ_FWD>(WqShape{m, n}, x, y, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_wpt2d_trees_f32(const float *x, float *y, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch, const double *qmf,
                        int F, void *stream)
-{ return api_wpt_trees2d<float, WQ_FWD>(x, y, m, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WQ_FWD>(WqShape{m, n}, x, y, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpt2d_trees_f64(const double *xw, double *xhat, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees2d<double, WQ_INV>(xw, xhat, m, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WQ_INV>(WqShape{m, n}, xw, xhat, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpt2d_trees_f32(const float *xw, float *xhat, int64_t m, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees2d<float, WQ_INV>(xw, xhat, m, n, 1, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WQ_INV>(WqShape{m, n}, xw, xhat, 1, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpd2d_trees_f64(const double *xw, double *xhat, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees2d<double, WQ_IWPD>(xw, xhat, m, n, k, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<double, WQ_IWPD>(WqShape{m, n}, xw, xhat, k, trees, ntree, batch, qmf, F, stream); }
 int wx_iwpd2d_trees_f32(const float *xw, float *xhat, int64_t m, int64_t n, int k, const uint8_t *trees, int64_t ntree, int64_t batch,
                         const double *qmf, int F, void *stream)
-{ return api_wpt_trees2d<float, WQ_IWPD>(xw, xhat, m, n, k, trees, ntree, batch, qmf, F, stream); }
+{ return wx_trees_api<float, WQ_IWPD>(WqShape{m, n}, xw, xhat, k, trees, ntree, batch, qmf, F, stream); }
 
 }  // extern "C"

@@ -311,49 +311,21 @@ def getbasiscoef(Xw, tree):
     return out.arr
 
 
-def _getbasiscoefall_device_trees(Xw, trees):
-    """getbasiscoefall with the trees in device memory: validated there, read by the gather where they are (csrc/wx_trees_prep.hip)"""
-    sig, k, N = Xw.shape[:-2], Xw.shape[-2], Xw.shape[-1]
-    tb, tp, nt = trees_arg(trees, N, Xw)
-    out = Xw.new(sig + (N,))
-    if len(sig) == 2:
-        _call("wx_getbasiscoef2d_trees", Xw.suffix, Xw.ptr, out.ptr, sig[0], sig[1], k, tp, nt, N, Xw.stream())
-    else:
-        _call("wx_getbasiscoef1d_trees", Xw.suffix, Xw.ptr, out.ptr, sig[0], k, tp, nt, N, Xw.stream())
-    return out.arr
-
-
 def getbasiscoefall(Xw, tree):
     """Utils.jl:169-225.  One tree per signal: a boolean (tree length, N) matrix, or a device tensor of torch.bool / torch.uint8
-    of that shape (bestbasistreeall(X, BB(), device=True)), which stays on the device."""
+    of that shape (bestbasistreeall(X, BB(), device=True)), which stays on the device: validated there, read by the gather where
+    it is (csrc/wx_trees_prep.hip)."""
     Xw = Arg(Xw)
     assert 3 <= Xw.arr.ndim <= 4                                      # Utils.jl:175
-    if _is_device_trees(tree):
-        return _getbasiscoefall_device_trees(Xw, tree)
-    tree = np.asarray(tree, dtype=bool)
-    if Xw.arr.ndim == 4:
-        mm, nn, k, N = Xw.shape
-        import ctypes
-        out = Xw.new((mm, nn, N))
-        if tree.ndim == 2:                                            # Utils.jl:199-225: one tree per image, one launch
-            assert N == tree.shape[1]
-            tb = np.asfortranarray(tree.astype(np.uint8))
-            _call("wx_getbasiscoef2d_trees", Xw.suffix, Xw.ptr, out.ptr, mm, nn, k, ctypes.c_void_p(tb.ctypes.data), tb.shape[0], N,
-                  Xw.stream())
-        else:
-            tk, tp, nt = tree_arg(tree)
-            _call("wx_getbasiscoef2d", Xw.suffix, Xw.ptr, out.ptr, mm, nn, k, tp, nt, N, Xw.stream())
-        return out.arr
-    n, k, m = Xw.shape
-    if tree.ndim == 2:                                                # Utils.jl:199-225: one tree per signal
-        nt, mt = tree.shape
-        assert m == mt
-        out = Xw.new((n, m))
-        import ctypes
-        tb = np.asfortranarray(tree.astype(np.uint8))                 # (ntree, m): column i = the tree of signal i
-        _call("wx_getbasiscoef1d_trees", Xw.suffix, Xw.ptr, out.ptr, n, k, ctypes.c_void_p(tb.ctypes.data), nt, m, Xw.stream())
-        return out.arr
-    tk, tp, nt = tree_arg(tree)
-    out = Xw.new((n, m))
-    _call("wx_getbasiscoef1d", Xw.suffix, Xw.ptr, out.ptr, n, k, tp, nt, m, Xw.stream())
+    if not _is_device_trees(tree):
+        tree = np.asarray(tree, dtype=bool)                           # any non-zero value is "decomposed", before the bytes are taken
+    sig, k, N = Xw.shape[:-2], Xw.shape[-2], Xw.shape[-1]
+    name = "wx_getbasiscoef%dd" % len(sig)
+    if tree.ndim == 2:                                                # Utils.jl:199-225: one tree per signal or image, one launch
+        tb, tp, nt = trees_arg(tree, N, Xw)                           # (ntree, N): column i = the tree of signal i
+        name += "_trees"
+    else:
+        tk, tp, nt = tree_arg(tree)
+    out = Xw.new(sig + (N,))
+    _call(name, Xw.suffix, Xw.ptr, out.ptr, *sig, k, tp, nt, N, Xw.stream())
     return out.arr
