@@ -336,6 +336,31 @@ int wx_iwpd2d_trees_f32(const float *xw, float *xhat, int64_t m, int64_t n, int 
  * 4 = device trees copied to the host (outside the window); 5 = device trees, prep launch + gather. */
 int wx_wpt_trees_last_route(void);
 
+/* denoise / denoiseall(xw, :wpt, wt; tree, dnt, estnoise, smooth) with ONE tree per signal: signal b is denoised in the basis of column b
+ * of `trees`.  The reference takes a single BitVector (Denoising.jl:483-599, 651-712); this is its loop with the (ntree, batch) convention
+ * of getbasiscoefall (Utils.jl:199-225), as wx_iwpt1d_trees_*.  For signal b with tree T_b:
+ *   sigma_b = noisest(xw[:, b], false, T_b) (Denoising.jl:214-232) = mad of the finest detail range of T_b (Utils.jl:416-436) / 0.6745, with
+ *             the arithmetic and the non-finite rules of wx_noisest_* (bit for bit);
+ *   xhat[:, b] = iwpt(threshold(xw[:, b], th_kind, sigma_b * scale), wt, T_b) (Denoising.jl:510-533), the threshold on rows [lo_b, n) with
+ *             lo_b = the end of the coarsest scaling range of T_b (Utils.jl:351-370) when undersmooth != 0, else 0; th_kind and the
+ *             rounding of the threshold as wx_threshold_* / wx_iwpt1d_thresh_*.
+ * xw, xhat: (n, batch); xw is not modified, xw == xhat returns WX_EARG.  qmf == NULL (wt = nothing): xhat receives the thresholded
+ * coefficients.  xhat == NULL: only sigma is computed.  thr != NULL (nthr = 1 or batch values, host or device): the thresholds before
+ * scaling, scale * thr[0] or scale * thr[b], and nothing is estimated (estnoise given as numbers, Denoising.jl:503-571).  sigma (optional,
+ * host or device, batch values): the estimates, or the thresholds used before scaling.
+ * trees: host or device, checked and packed exactly as for wx_iwpt1d_trees_* (the first offending column decides; a rejected call has
+ * written nothing), and the routes are those: inside that window one launch (csrc/wx_denoise_trees.hip: the signal, its tree, the
+ * estimate, the threshold and the inverse in LDS); byte-identical columns go to wx_noisest_* + wx_iwpt1d_thresh_* on the one tree;
+ * outside the window those two run once per signal: correct and slow.  wx_wpt_trees_last_route reports the route of these calls too.
+ * Before a device is needed: bad dimensions, NULL trees, th_kind outside 0 .. 3, nthr not 0, 1 or batch (0 exactly when thr == NULL),
+ * neither xhat nor sigma: WX_EARG; n not dyadic, ntree != n - 1, an invalid tree: WX_EASSERT.  batch == 0 is WX_OK. */
+int wx_denoise_wpt1d_trees_f64(const double *xw, double *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                               const double *qmf, int F, int th_kind, double scale, const double *thr, int64_t nthr, int undersmooth,
+                               double *sigma, void *stream);
+int wx_denoise_wpt1d_trees_f32(const float *xw, float *xhat, int64_t n, const uint8_t *trees, int64_t ntree, int64_t batch,
+                               const double *qmf, int F, int th_kind, double scale, const float *thr, int64_t nthr, int undersmooth,
+                               float *sigma, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Standard (per-signal) best basis, BB -- SURVEY 8(f) row 3, widened after the 8(a) rows.

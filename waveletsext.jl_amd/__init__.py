@@ -26,7 +26,7 @@ from .bestbasis import (JBB, LoglpCost, NormCost, tree_costs, bestbasistree, bes
                         BB, ShannonEntropyCost, LogEnergyEntropyCost, bestbasistreeall,
                         LSDB, DifferentialEntropyCost, lsdb_entropy)
 from .denoising import (HardTH, SoftTH, SemiSoftTH, SteinTH, VisuShrink, SureShrink, RelErrorShrink,   # noqa: F401,E402
-                        noisest, threshold, denoise, denoiseall, surethreshold, relerrorthreshold,
+                        noisest, noisestall, threshold, denoise, denoiseall, surethreshold, relerrorthreshold,
                         surethresholdall, relerrorthresholdall)
 from .ldb import (TimeFrequency, AsymmetricRelativeEntropy, SymmetricRelativeEntropy, LpDistance,        # noqa: F401,E402
                   HellingerDistance, EarthMoverDistance, ProbabilityDensity, Signatures, SignatureMap, BasisDiscriminantMeasure,

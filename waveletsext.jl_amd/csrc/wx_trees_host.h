@@ -14,12 +14,17 @@
 // wx_trees_prep.  Byte-identical columns go to the single-tree entry whole; outside the window the single-tree entry runs once per
 // item (slow, correct), a device matrix coming to the host first.  The host route returns after the stream has finished, because
 // it uploads from memory of the call; the device route with device data waits for nothing but the prep record.
+// A shape with `static constexpr bool extras = true` carries more arguments than these (wx_denoise_trees.hip: thresholds, estimates); then
+//   S at(b)                            the shape of item b alone, for the single-tree entry once per item
+//   bool stage(io, batch)              its own arrays as device pointers for launch(), through the call's WxIO
+// and y and qmf may be NULL where the shape's check() admits it.
 #pragma once
 #include "../../include/waveletsext_hip.h"
 #include "wx_common.h"
 #include "wx_host.h"
 #include "wx_tree_bits.h"
 #include "wx_trees_prep.h"
+#include <type_traits>
 #include <vector>
 
 #define WX_REQUIRE(cond, code, msg) \
@@ -28,6 +33,9 @@
 extern "C" int wx_device_count(void);
 
 enum { WX_TREES_FWD = 0, WX_TREES_INV = 1, WX_TREES_IWPD = 2 };
+
+template <typename S, typename = void> struct WxTreesExtras { static constexpr bool value = false; };
+template <typename S> struct WxTreesExtras<S, std::void_t<decltype(S::extras)>> { static constexpr bool value = S::extras; };
 
 // one lane per output pair of a level or pass, at most 1024
 inline int wx_trees_threads(int64_t count)
@@ -72,8 +80,11 @@ int wx_trees_from_host(const S &s, const T *x, T *y, int k, const uint8_t *trees
     if (same) return s.single(MODE, x, y, k, trees, ntree, batch, qmf, F, stream);
     // outside the LDS kernel's window: the single-tree path once per item.  Slow (a tree upload and a launch sequence per item).
     if (!lds_path) {
-        for (int64_t b = 0; b < batch; ++b)
-            if ((rc = s.single(MODE, x + b * xs, y + b * cnt, k, trees + b * ntree, ntree, 1, qmf, F, stream))) return rc;
+        for (int64_t b = 0; b < batch; ++b) {
+            if constexpr (WxTreesExtras<S>::value) rc = s.at(b).single(MODE, x + b * xs, y ? y + b * cnt : y, k, trees + b * ntree, ntree, 1, qmf, F, stream);
+            else rc = s.single(MODE, x + b * xs, y + b * cnt, k, trees + b * ntree, ntree, 1, qmf, F, stream);
+            if (rc) return rc;
+        }
         return WX_OK;
     }
     hipStream_t st = wx_stream(stream);
@@ -84,8 +95,10 @@ int wx_trees_from_host(const S &s, const T *x, T *y, int k, const uint8_t *trees
     uint8_t *dd = dt + tbytes;
     WxIO io(st);
     const T *dx = (const T *)io.in(x, sizeof(T) * xs * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * cnt * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
+    T *dy = WxTreesExtras<S>::value && !y ? nullptr : (T *)io.out(y, sizeof(T) * cnt * batch);
+    if (!dx || (!dy && (y || !WxTreesExtras<S>::value))) return io.finish(WX_EHIP);
+    if constexpr (WxTreesExtras<S>::value)
+        if (!s.stage(io, batch)) return io.finish(WX_EHIP);
     // the packed trees go over from pageable memory of this call: every return behind these copies waits for the stream first.  (The
     // caller's matrix is not read past this point: it may be released on return, as with wx_getbasiscoef*_trees_*.)
     hipError_t e = hipMemcpyAsync(dt, bits.data(), tbytes, hipMemcpyHostToDevice, st);
@@ -144,8 +157,10 @@ int wx_trees_from_device(const S &s, const T *x, T *y, int k, const uint8_t *tre
     }
     WxIO io(st);
     const T *dx = (const T *)io.in(x, sizeof(T) * cnt * (MODE == WX_TREES_IWPD ? k : 1) * batch);
-    T *dy = (T *)io.out(y, sizeof(T) * cnt * batch);
-    if (!dx || !dy) return io.finish(WX_EHIP);
+    T *dy = WxTreesExtras<S>::value && !y ? nullptr : (T *)io.out(y, sizeof(T) * cnt * batch);
+    if (!dx || (!dy && (y || !WxTreesExtras<S>::value))) return io.finish(WX_EHIP);
+    if constexpr (WxTreesExtras<S>::value)
+        if (!s.stage(io, batch)) return io.finish(WX_EHIP);
     const hipError_t e = s.template launch<T, MODE>(dx, dy, ntree, k, batch, (const uint32_t *)dt, dd, filt, st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
@@ -161,7 +176,9 @@ int wx_trees_api(const S &s, const T *x, T *y, int k, const uint8_t *trees, int6
 {
     wx_trees_route_set(WX_TREES_ROUTE_NONE);
     WxFilt filt;
-    int rc = wx_pack_filter(qmf, F, &filt);
+    int rc = WX_OK;
+    if (WxTreesExtras<S>::value && !qmf) filt.F = 0;                   // no transform (the shape's check() decides whether that is allowed)
+    else rc = wx_pack_filter(qmf, F, &filt);
     if (rc) return rc;
     // argument errors are reported before any device is needed, with the codes of the single-tree entries and of getbasiscoefall
     WX_REQUIRE(s.dims_ok() && batch >= 0 && k >= 1, WX_EARG, "wptall(trees): bad dimensions");

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._arrays import Arg, to_numpy
+from ._arrays import Arg, is_torch, to_numpy
 from .dwt import dwt, dwtall, idwt, idwtall, iwpt, iwptall
 from .swt import isdwt, isdwtall, iswpd, iswpdall
 from .acwt import iacdwt, iacdwtall, iacwpd, iacwpdall
@@ -204,12 +204,75 @@ def _denoise_sig(xa, wt, L, dnt, smooth, batched, entry="wx_denoiseall_sig"):
     return out.arr
 
 
+def _is_tree_matrix(tree):
+    """one tree per signal: an (n - 1, N) matrix, on the host or (bestbasistreeall(..., device=True)) on the device"""
+    if is_torch(tree):
+        return tree.dim() == 2
+    return tree is not None and np.ndim(tree) == 2
+
+
+def _trees_call(xa, N, wt, trees, th_kind, scale, thr, smooth, want_out, want_sigma):
+    """wx_denoise_wpt1d_trees_*: (xhat | None, sigma | None) as Args of the input's kind; thr: None (the noise is estimated per signal, each
+    on the finest detail node of its own tree) or 1 / N host values, the thresholds before scaling"""
+    from ._arrays import qmf_arg, trees_arg
+    null = ctypes.c_void_p(0)
+    q, qp, F = (None, null, 0) if wt is None else qmf_arg(wt)
+    tb, tp, nt = trees_arg(trees, N, xa)
+    out = xa.new(xa.shape) if want_out else None
+    sig = xa.new((N,)) if want_sigma else None
+    tv = None if thr is None else np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=xa.dtype)))
+    fn = getattr(_lib.lib(), "wx_denoise_wpt1d_trees" + xa.suffix)
+    _lib.check(fn(xa.ptr, out.ptr if want_out else null, xa.shape[0], tp, nt, N, qp, F, int(th_kind), float(scale),
+                  null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
+                  1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream()))
+    return out, sig
+
+
+def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batched):
+    """denoise / denoiseall(x, :wpt, wt; tree = M) with M an (n - 1, N) matrix: signal i in the basis of column i (csrc/wx_denoise_trees.hip)"""
+    if inputtype != "wpt":
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs inputtype = :wpt")
+    if xa.arr.ndim != (2 if batched else 1):
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals")
+    N = xa.shape[-1] if batched else 1
+    if estnoise is None or estnoise is noisest:
+        thr = None
+    elif estnoise is relerrorthreshold or estnoise is surethreshold:
+        # all coefficients of a non-redundant signal, whatever its tree (Denoising.jl:150-157, 293-300)
+        thr = _select(xa, batched, False, None, 1 if estnoise is relerrorthreshold else 0)
+    elif callable(estnoise):
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED,
+                           "noise estimates on the device path: noisest, relerrorthreshold, surethreshold or precomputed values")
+    else:
+        thr = np.broadcast_to(np.asarray(estnoise, dtype=np.float64), (N,)).astype(xa.dtype)
+    if bestTH is not None:                                             # one summary threshold for the batch, Denoising.jl:697-700
+        if thr is None:
+            thr = to_numpy(_trees_call(xa, N, None, trees, dnt.th.kind, dnt.t, None, smooth, False, True)[1].arr)
+        thr = np.full(1, bestTH(np.asarray(thr, dtype=np.float64)), dtype=xa.dtype)
+    return _trees_call(xa, N, wt, trees, dnt.th.kind, dnt.t, thr, smooth, True, False)[0].arr
+
+
+def noisestall(x, redundant=False, tree=None):
+    """noisest (Denoising.jl:214-232) of every signal of a batch (last axis): `tree` is None, one tree for all, or an (n - 1, N) matrix with
+    the tree of signal i in column i (then each estimate comes from the finest detail node of its own tree)"""
+    xa = Arg(x)
+    if _is_tree_matrix(tree):
+        if redundant or xa.arr.ndim != 2:
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs non-redundant 1-D signals")
+        return _trees_call(xa, xa.shape[-1], None, tree, 0, 1.0, None, "regular", False, True)[1].arr
+    it = ("sdwt" if tree is None else "swpd") if redundant else ("dwt" if tree is None else "wpt")
+    sig = _noisest(xa, True, it, None if tree is None else np.asarray(tree, dtype=bool), on_device=xa.kind == "torch")
+    return sig.arr if isinstance(sig, Arg) else sig
+
+
 def _denoise(x, inputtype, wt, L, tree, dnt, estnoise, bestTH, smooth, batched):
     assert smooth in ("undersmooth", "regular")                       # Denoising.jl:493
     assert inputtype in INPUTTYPES                                     # Denoising.jl:494
     if not isinstance(dnt, (VisuShrink, SureShrink, RelErrorShrink)):
         raise _lib.WxError(_lib.WX_EARG, "dnt must be a VisuShrink, SureShrink or RelErrorShrink")
     xa = Arg(x)
+    if _is_tree_matrix(tree):
+        return _denoise_trees(xa, inputtype, wt, tree, dnt, estnoise, bestTH, smooth, batched)
     n = xa.shape[0]
     L = maxtransformlevels(n) if L is None else int(L)
     tree = maketree(n, L, "dwt") if tree is None else np.asarray(tree, dtype=bool)

@@ -820,6 +820,27 @@ function denoiseall_sig(x::HIP{T,2}, wt::OrthoFilter, L::Integer, th::THType, t:
     end
     return x̂
 end
+"iwptall(threshold(xw, th, σ .* t), wt, trees) with one tree per signal (column i of `trees` for signal i) and σᵢ = noisest(xwᵢ, false, treeᵢ),
+or σ = thr (one value, or one per signal): one launch (wx_denoise_wpt1d_trees_*); wt = nothing returns the thresholded coefficients"
+function denoiseall_trees(xw::HIP{T,2}, wt::Union{OrthoFilter,Nothing}, trees::BitMatrix, th::THType, t::Real, undersmooth::Bool;
+                          thr::Union{Vector{T},Nothing} = nothing) where T<:FT
+    n, N = size(xw)
+    @assert size(trees, 2) == N
+    x̂ = newlike(xw, T, (n, N)); tb = Matrix{UInt8}(trees)
+    q = wt === nothing ? C_NULL : qmfvec(wt)
+    check(wx_denoise_wpt1d_trees(T, raw(xw), x̂, n, tb, size(tb, 1), N, q, wt === nothing ? 0 : length(q), thkind(th), Float64(t),
+                                 thr === nothing ? C_NULL : thr, thr === nothing ? 0 : length(thr), undersmooth ? 1 : 0, C_NULL, stream()))
+    return x̂
+end
+"noisest of every signal on the finest detail node of its own tree (column i of `trees`)"
+function noisestall(xw::HIP{T,2}, redundant::Bool, trees::BitMatrix) where T<:FT
+    redundant && throw(ArgumentError("a tree matrix (one tree per signal) needs non-redundant coefficients"))
+    n, N = size(xw)
+    @assert size(trees, 2) == N
+    sigma = Vector{T}(undef, N); tb = Matrix{UInt8}(trees)
+    check(wx_denoise_wpt1d_trees(T, raw(xw), C_NULL, n, tb, size(tb, 1), N, C_NULL, 0, 0, 1.0, C_NULL, 0, 0, sigma, stream()))
+    return sigma
+end
 # surethreshold / relerrorthreshold of one signal (Denoising.jl:146-166, 285-327) and of every signal of a batch (what
 # SureShrink(xw, redundant, tree) and denoiseall(...; estnoise = relerrorthreshold) evaluate signal by signal)
 function surethresholdall(coef::HIP{T}, redundant::Bool, tree::Union{BitVector,Nothing} = nothing; batched::Bool = true) where T<:FT
@@ -846,13 +867,24 @@ relerrorthreshold(coef::HIP{T}, redundant::Bool = false, tree::Union{BitVector,N
 # denoiseall(x, :sig | :dwt | :wpt, wt; ...) (Denoising.jl:651-712) for the VisuShrink family as one device pipeline:
 # transform, MAD of every signal, threshold riding on the inverse's loads.  The redundant input types compose from
 # noisestall / thresholdall! and the inverse batch methods above exactly as waveletsext.jl_amd/denoising.py does.
+#
+# tree::BitMatrix (keywords do not dispatch, so the same method takes it): one tree per signal, column i for signal i -- the BitMatrix
+# convention of getbasiscoefall, what bestbasistreeall(X, BB()) returns.  Every signal is denoised in its own basis by one launch
+# (denoiseall_trees below); inputtype is :wpt then.
 function WaveletsExt.Denoising.denoiseall(x::HIP{T,2}, inputtype::Symbol, wt::OrthoFilter;
-        L::Integer = maxtransformlevels(size(x, 1)), tree::BitVector = maketree(size(x, 1), L, :dwt),
+        L::Integer = maxtransformlevels(size(x, 1)), tree::Union{BitVector,BitMatrix} = maketree(size(x, 1), L, :dwt),
         dnt = VisuShrink(size(x, 1)), estnoise::Union{Function,Vector{<:Number}} = noisest,
         bestTH::Union{Function,Nothing} = nothing, smooth::Symbol = :regular) where T<:FT
     @assert smooth in (:undersmooth, :regular)
     inputtype in (:sig, :dwt, :wpt) || throw(ArgumentError("device pipeline: inputtype :sig, :dwt or :wpt (compose the redundant types from noisestall / thresholdall!)"))
     estnoise isa Function && estnoise !== noisest && throw(ArgumentError("device pipeline: estnoise = noisest or precomputed values"))
+    if tree isa BitMatrix
+        inputtype === :wpt || throw(ArgumentError("a tree matrix (one tree per signal) needs inputtype = :wpt"))
+        # the estimates stay inside the launch unless a summary threshold needs them (Denoising.jl:697-700)
+        σ = estnoise isa Function ? (bestTH === nothing ? nothing : noisestall(x, false, tree)) : Vector{T}(estnoise)
+        bestTH === nothing || (σ = T[bestTH(σ)])
+        return denoiseall_trees(x, wt, tree, dnt.th, dnt.t, smooth === :undersmooth; thr = σ)
+    end
     n = size(x, 1)
     if inputtype in (:sig, :dwt) && estnoise === noisest && bestTH === nothing
         # the whole pipeline behind one entry point (one pass over the signals / coefficients where the lattice kernel applies)
