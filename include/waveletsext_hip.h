@@ -361,6 +361,27 @@ int wx_denoise_wpt1d_trees_f32(const float *xw, float *xhat, int64_t n, const ui
                                const double *qmf, int F, int th_kind, double scale, const float *thr, int64_t nthr, int undersmooth,
                                float *sigma, void *stream);
 
+/* iswpdall / iacwpdall with ONE tree per signal: signal b goes back from its redundant packet table xw[:, :, b] (wx_swpd1d_*,
+ * wx_acwpd1d_*: heap ordered, node i in column i - 1) along column b of `trees`.  The reference takes a single BitVector for the batch
+ * (swt/swt_all.jl:343-392 over iswpd!, SWT.jl:1063-1093 shift based and 1137-1160 average based; acwt/acwt_all.jl:300-333 over iacwpd!,
+ * ACWT.jl:944-968); this is its loop with the (ntree, batch) convention of getbasiscoefall (Utils.jl:199-225), as wx_iwpd1d_trees_*.
+ * xw: (n, ncols, batch), x: (n, batch); sm < 0: average based, sm >= 0: shift based with main2depthshift (Utils.jl:297-305) on the
+ * table's depth getdepth(ncols, :binary).  The autocorrelation entry is Float64 only and takes no filter.
+ * trees: host or device, checked and packed exactly as for wx_iwpt1d_trees_* (the lowest offending column decides; a rejected call has
+ * written nothing).  Routes: inside the window -- n dyadic >= 8, even filters of 2 .. 20 taps, 2 D n sizeof(T) + the tree bits + 512
+ * bytes <= 136 KiB with D the deepest tree the table holds, i.e. Float64 every depth up to n = 512 and depth 8 at n = 1024 -- one launch
+ * (csrc/wx_red_trees.hip: a depth-first walk of the signal's tree in LDS, no scratch memory); byte-identical columns go to wx_iswpd1d_* /
+ * wx_iacwpd1d_f64 whole; outside the window those run once per signal: correct and slow.  wx_wpt_trees_last_route reports the route.
+ * Before a device is needed, with the codes of the single-tree entries: bad dimensions, x == xw, NULL trees (or NULL qmf): WX_EARG;
+ * n not dyadic, ntree != n - 1, sm >= 2^getdepth(ncols), an invalid column: WX_EASSERT; a column deeper than the table (2^(depth + 1) - 1 >
+ * ncols): WX_EBOUNDS.  batch == 0 is WX_OK. */
+int wx_iswpd1d_trees_f64(const double *xw, double *x, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t sm,
+                         int64_t batch, const double *qmf, int F, void *stream);
+int wx_iswpd1d_trees_f32(const float *xw, float *x, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t sm,
+                         int64_t batch, const double *qmf, int F, void *stream);
+int wx_iacwpd1d_trees_f64(const double *xw, double *x, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch,
+                          void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Standard (per-signal) best basis, BB -- SURVEY 8(f) row 3, widened after the 8(a) rows.

@@ -125,6 +125,8 @@ _EXTRA_SIGS = {
     "wx_iwpt2d_trees": [_P, _P, _L, _L, _P, _L, _L, _P, _I, _P],
     "wx_iwpd2d_trees": [_P, _P, _L, _L, _I, _P, _L, _L, _P, _I, _P],
     "wx_denoise_wpt1d_trees": [_P, _P, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
+    "wx_iswpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _L, _P, _I, _P],
+    "wx_iacwpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _P],
     "wx_jbb_moments": [_P, _P, _P, _L, _L, _I, _P],
     "wx_jbb_costs": [_P, _P, _L, _L, _L, _I, _I, ctypes.c_double, _P, _P],
     "wx_acwpd_jbb_moments": [_P, _P, _P, _L, _I, _L, _P, _I, _I, _P],
@@ -305,7 +307,7 @@ WPT_TREES_ROUTES = {0: "none", 1: "host trees", 2: "device prep + lds kernel", 3
 
 
 def wpt_trees_route():
-    """which way the last wptall / iwptall / iwpdall / getbasiscoefall call with one tree per signal went on this thread
+    """which way the last wptall / iwptall / iwpdall / getbasiscoefall / denoiseall / iswpdall / iacwpdall call with one tree per signal went on this thread
     (wx_wpt_trees_last_route): one of WPT_TREES_ROUTES' strings; "none" before the first such call and after one that raised"""
     return WPT_TREES_ROUTES[lib().wx_wpt_trees_last_route()]
 

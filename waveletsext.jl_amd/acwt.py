@@ -3,10 +3,10 @@
 (`iacdwt(xw)` / `iacdwt(xw, wt)` are both accepted, like the reference)."""
 import numpy as np
 
-from ._arrays import Arg, out_arg, tree_arg
+from ._arrays import Arg, out_arg, tree_arg, trees_arg
 from .dwt import _call, _split_Ltree
 from .filters import ArgumentError, OrthoFilter
-from .swt import _fwd, _inv_common
+from .swt import _fwd, _inv_common, _is_tree_matrix, _req_trees_1d
 from .util import isdyadic, maxtransformlevels, ndyadicscales
 
 
@@ -175,6 +175,13 @@ def _iacwpd(xw, L_or_tree, batched, x=None):
         assert tuple(x.shape)[:1] == sig[:1]                                       # ACWT.jl:946
         assert tuple(x.shape) == sig + ((N,) if batched else ())
     out = xw.new(sig + ((N,) if batched else ())) if x is None else out_arg(x, xw)
+    if _is_tree_matrix(tree):
+        # one tree per signal, column i the tree of signal i (csrc/wx_red_trees.hip); a single signal takes a one-column matrix
+        _req_trees_1d(len(sig))
+        B = 1 if N is None else N
+        tb, tp, nt = trees_arg(tree, B, xw)
+        _call("wx_iacwpd1d_trees", "_f64", xw.ptr, out.ptr, sig[0], m, tp, nt, B, xw.stream())
+        return out.arr if x is None else x
     tk, tp, nt = tree_arg(tree)
     if len(sig) == 1:
         _call("wx_iacwpd1d", "_f64", xw.ptr, out.ptr, sig[0], m, L, tp, nt, 1 if N is None else N, xw.stream())

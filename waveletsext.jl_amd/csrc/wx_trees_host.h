@@ -18,6 +18,10 @@
 //   S at(b)                            the shape of item b alone, for the single-tree entry once per item
 //   bool stage(io, batch)              its own arrays as device pointers for launch(), through the call's WxIO
 // and y and qmf may be NULL where the shape's check() admits it.
+// A shape with `static constexpr bool table = true` reads each item from a table of its own (wx_red_trees.hip: the redundant packet tables) and has
+//   int64_t in_count()                 elements of one input item
+//   int tree_k()                       no tree may be as deep as this: the `k` of the trees' check, whatever the mode
+//   int too_deep()                     the error of a tree that is, with the code and message of the shape's single-tree entry
 #pragma once
 #include "../../include/waveletsext_hip.h"
 #include "wx_common.h"
@@ -36,6 +40,20 @@ enum { WX_TREES_FWD = 0, WX_TREES_INV = 1, WX_TREES_IWPD = 2 };
 
 template <typename S, typename = void> struct WxTreesExtras { static constexpr bool value = false; };
 template <typename S> struct WxTreesExtras<S, std::void_t<decltype(S::extras)>> { static constexpr bool value = S::extras; };
+template <typename S, typename = void> struct WxTreesTable { static constexpr bool value = false; };
+template <typename S> struct WxTreesTable<S, std::void_t<decltype(S::table)>> { static constexpr bool value = S::table; };
+
+// elements of one input item, and the depth no tree may reach (0: any)
+template <int MODE, typename S> inline int64_t wx_trees_in_count(const S &s, int k)
+{
+    if constexpr (WxTreesTable<S>::value) return s.in_count();
+    else return MODE == WX_TREES_IWPD ? s.count() * k : s.count();
+}
+template <int MODE, typename S> inline int wx_trees_k(const S &s, int k)
+{
+    if constexpr (WxTreesTable<S>::value) return s.tree_k();
+    else return MODE == WX_TREES_IWPD ? k : 0;
+}
 
 // one lane per output pair of a level or pass, at most 1024
 inline int wx_trees_threads(int64_t count)
@@ -67,11 +85,13 @@ int wx_trees_from_host(const S &s, const T *x, T *y, int k, const uint8_t *trees
     // same pass.
     const bool lds_path = s.template window<T>(ntree, F);
     const int nw = wq_words(ntree);
-    const int64_t cnt = s.count(), xs = MODE == WX_TREES_IWPD ? cnt * k : cnt;
+    const int64_t cnt = s.count(), xs = wx_trees_in_count<MODE>(s, k);
     std::vector<uint8_t> depths((size_t)(batch > 0 ? batch : 1));
     std::vector<uint32_t> bits(lds_path ? (size_t)nw * batch : 0);     // zero-initialised
     bool same = true;
-    int rc = s.check_host(trees, ntree, batch, MODE == WX_TREES_IWPD ? k : 0, lds_path ? bits.data() : nullptr, nw, depths.data(), &same);
+    int rc = s.check_host(trees, ntree, batch, wx_trees_k<MODE>(s, k), lds_path ? bits.data() : nullptr, nw, depths.data(), &same);
+    if constexpr (WxTreesTable<S>::value)
+        if (rc == WX_EARG) return s.too_deep();
     if (rc == WX_EARG) return wx_set_error(WX_EARG, "getbasiscoef: Not enough decomposition levels in Xw (Utils.jl:120)");
     if (rc) return rc;
     if (batch == 0) return WX_OK;
@@ -148,7 +168,9 @@ int wx_trees_from_device(const S &s, const T *x, T *y, int k, const uint8_t *tre
     uint8_t *dd = dt + tbytes;
     std::vector<uint8_t> col0((size_t)ntree);
     bool same = true;
-    int rc = wx_trees_prep(S::quad, trees, ntree, batch, MODE == WX_TREES_IWPD ? k : 0, (uint32_t *)dt, nw, dd, col0.data(), &same, st);
+    int rc = wx_trees_prep(S::quad, trees, ntree, batch, wx_trees_k<MODE>(s, k), (uint32_t *)dt, nw, dd, col0.data(), &same, st);
+    if constexpr (WxTreesTable<S>::value)
+        if (rc == WX_EARG) return s.too_deep();
     if (rc) return rc;                                                 // nothing has been written to y
     if (same) {                                                        // one tree after all: as the host path does, with the same result
         rc = s.single(MODE, x, y, k, col0.data(), ntree, batch, qmf, F, stream);
@@ -156,7 +178,7 @@ int wx_trees_from_device(const S &s, const T *x, T *y, int k, const uint8_t *tre
         return rc;
     }
     WxIO io(st);
-    const T *dx = (const T *)io.in(x, sizeof(T) * cnt * (MODE == WX_TREES_IWPD ? k : 1) * batch);
+    const T *dx = (const T *)io.in(x, sizeof(T) * wx_trees_in_count<MODE>(s, k) * batch);
     T *dy = WxTreesExtras<S>::value && !y ? nullptr : (T *)io.out(y, sizeof(T) * cnt * batch);
     if (!dx || (!dy && (y || !WxTreesExtras<S>::value))) return io.finish(WX_EHIP);
     if constexpr (WxTreesExtras<S>::value)

@@ -571,6 +571,19 @@ for AT in (:Integer, :BitVector), smsig in ((), (:(sm::Integer),))
         end
     end
 end
+# one tree per signal (column i of `trees` for signal i, what bestbasistreeall(X, BB(redundant = true)) returns): every signal goes back
+# from its stationary packet table along its own basis, one launch (csrc/wx_red_trees.hip).  Bytes under the marker wrapper cross as
+# their pointer and may live on the device, as for iwpdall above.
+treesarg(trees::BitMatrix) = Matrix{UInt8}(trees)
+treesarg(trees::HIP{UInt8,2}) = raw(trees)
+function iswpdall(xw::HIP{T,3}, wt::OrthoFilter, trees::Union{BitMatrix,HIP{UInt8,2}}, sm::Union{Integer,Nothing} = nothing) where T<:FT
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x = newlike(xw, T, (n, N))
+    q = qmfvec(wt)
+    check(wx_iswpd1d_trees(T, raw(xw), x, n, k, treesarg(trees), size(trees, 1), smarg(sm), N, q, length(q), stream()))
+    return x
+end
 
 # ---------------------------------------------------------------------------------------------------------------------
 # inverse autocorrelation transforms -- ACWT.jl, acwt/acwt_all.jl (1-D and 2-D, Float64)
@@ -643,6 +656,15 @@ for AT in (:Integer, :BitVector)
         iacwpdall(xw::HIP{T}, wt::Union{OrthoFilter,Nothing}, arg::$AT) where T<:FT = iacwpdall(xw, arg)
     end
 end
+# one tree per signal, as iswpdall(xw, wt, trees) above (wx_iacwpd1d_trees_f64: Float64 only, no filter)
+function iacwpdall(xw::HIP{Float64,3}, trees::Union{BitMatrix,HIP{UInt8,2}})
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    x = newlike(xw, Float64, (n, N))
+    check(wx_iacwpd1d_trees(Float64, raw(xw), x, n, k, treesarg(trees), size(trees, 1), N, stream()))
+    return x
+end
+iacwpdall(xw::HIP{Float64,3}, wt::Union{OrthoFilter,Nothing}, trees::Union{BitMatrix,HIP{UInt8,2}}) = iacwpdall(xw, trees)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # best basis -- bestbasis/bestbasis_tree.jl:150-258, BestBasis.jl:59-110, 194-262

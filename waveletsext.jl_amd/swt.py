@@ -2,7 +2,7 @@
 (src/mod/SWT.jl, src/mod/swt/swt_all.jl) for 1-D signals.  `sm=None` selects the average-based
 inverse, an integer the shift-based one.  Mutating forms carry a trailing underscore."""
 from . import _lib
-from ._arrays import Arg, out_arg, qmf_arg, tree_arg
+from ._arrays import Arg, out_arg, qmf_arg, tree_arg, trees_arg
 from .dwt import _call, _split_Ltree
 from .filters import ArgumentError
 from .util import isdyadic, maxtransformlevels, ndyadicscales
@@ -11,6 +11,17 @@ from .util import isdyadic, maxtransformlevels, ndyadicscales
 def _req_1d(nd):
     if nd not in (1, 2):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED, "redundant transforms are implemented for 1-D and 2-D signals")
+
+
+def _is_tree_matrix(tree):
+    from .denoising import _is_tree_matrix as f                      # denoising imports this module
+    return f(tree)
+
+
+def _req_trees_1d(nd):
+    if nd != 1:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals: quad-tree matrices are not "
+                                                 "taken for redundant tables")
 
 
 def _ncols(kind, L, nd):
@@ -194,6 +205,13 @@ def _iswpd(xw, wt, L_or_tree, sm, batched, x=None):
         assert tuple(x.shape) == sig + ((N,) if batched else ())      # SWT.jl:1039
     out = xw.new(sig + ((N,) if batched else ())) if x is None else out_arg(x, xw)
     q, qp, F = qmf_arg(wt)
+    if _is_tree_matrix(tree):
+        # one tree per signal, column i the tree of signal i (csrc/wx_red_trees.hip); a single signal takes a one-column matrix
+        _req_trees_1d(len(sig))
+        B = 1 if N is None else N
+        tb, tp, nt = trees_arg(tree, B, xw)
+        _call("wx_iswpd1d_trees", xw.suffix, xw.ptr, out.ptr, sig[0], m, tp, nt, _smv(sm), B, qp, F, xw.stream())
+        return out.arr if x is None else x
     tk, tp, nt = tree_arg(tree)
     if len(sig) == 1:
         _call("wx_iswpd1d", xw.suffix, xw.ptr, out.ptr, sig[0], m, L, tp, nt, _smv(sm), 1 if N is None else N, qp, F,
