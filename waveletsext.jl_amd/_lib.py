@@ -58,6 +58,8 @@ def _declare(L):
     L.wx_debug_swt1d_trace_dropped.restype = _L
     L.wx_debug_swt_inv_plan.argtypes = [_I, _I, _I, _L, _L, _I, _I, _I, _P]
     L.wx_debug_swt_inv_plan.restype = _I
+    L.wx_debug_ldb_chunks.argtypes = [_L, _L, _I]
+    L.wx_debug_ldb_chunks.restype = _I
     sigs = {
         # name: argtypes (without the _f64/_f32 suffix)
         "wx_wpd1d": [_P, _P, _L, _I, _L, _P, _I, _P],
@@ -355,3 +357,11 @@ def swt_inv_plan(layout, L, F, n, elem_size, sm=None, has_tree=False, haar6=Fals
                                       int(bool(has_tree)), int(bool(haar6)), out.ctypes.data)
     check(min(got, 0))
     return [tuple(r) for r in out[:got].tolist()]
+
+
+def ldb_chunks(nk, N, nc):
+    """chunks per class of the LDB class reductions (energy map, class means / variances) over nk coefficients of N signals in nc
+    classes (csrc/wx_debug.h: wx_debug_ldb_chunks, which runs the function the launch code calls; needs no device)"""
+    got = lib().wx_debug_ldb_chunks(int(nk), int(N), int(nc))
+    check(min(got, 0))
+    return got

@@ -81,6 +81,12 @@ int wx_debug_swt_inv_plan(int layout, int L, int F, int64_t sm, int64_t n, int e
  * n - 1 bytes (any non-zero byte = decomposed), words receives max(n / 32, 1) words with the bits past node n - 1 zero.  Needs no
  * device.  Returns the number of words, or WX_EARG (-2) for a NULL pointer or n < 2. */
 int wx_debug_pack_tree1d(const uint8_t *tree, int64_t n, uint32_t *words);
+
+/* The number of chunks every class's signals are split into by the LDB class reductions (wx_ldb.hip: wx_energy_map_*, wx_class_mean_*,
+ * wx_class_var_*) over nk coefficients of N signals in nc classes, by the very function the launch code calls: one workgroup row per
+ * class and chunk, chunks of at least 64 signals of the average class, classes x chunks <= 65535.  Needs no device.  Returns
+ * WX_EARG (-2) for arguments those entry points refuse: nk < 1, N outside 1 .. 2^31 - 1, nc outside 2 .. 65535. */
+int wx_debug_ldb_chunks(int64_t nk, int64_t N, int nc);
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,7 @@
 // wx_getbasiscoef* + an index selection.
 #include "../../include/waveletsext_hip.h"     // the definitions below must match the public prototypes
 #include "wx_common.h"
+#include "wx_debug.h"
 #include "wx_host.h"
 #include "wx_kernels.h"
 
@@ -129,15 +130,17 @@ int check_labels(const int32_t *cls, int64_t N, int nc, bool allow_empty)
     return WX_OK;
 }
 
-int pick_chunks(int64_t nk, int64_t N)
+// chunks per class of a reduction over nk coefficients of N signals in nc classes (wx_debug_ldb_chunks reports it)
+int ldb_chunks(int64_t nk, int64_t N, int nc)
 {
-    // enough workgroups to fill the chip: ceil(nk/256) * nchunks >= ~2048, chunks of at least 64 signals
+    // enough workgroups to fill the chip: ceil(nk/256) * nchunks >= ~2048, chunks of at least 64 signals of the average class
     int64_t gx = (nk + 255) / 256;
     int64_t want = (2048 + gx - 1) / gx;
-    int64_t maxc = (N + 63) / 64;
+    int64_t maxc = ((N + nc - 1) / nc + 63) / 64;
     if (want > maxc) want = maxc;
     if (want < 1) want = 1;
     if (want > 1024) want = 1024;
+    if (want * nc > LDB_MAXC) want = LDB_MAXC / nc;                // gridDim.y
     return (int)want;
 }
 
@@ -176,8 +179,7 @@ int api_class_reduce(const T *X, int64_t nk, int64_t nroot, int64_t N, const int
         hipMemcpyAsync(doffs, offs.data(), sizeof(int) * ((size_t)nc + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)                    // the host vectors go out of scope
         return io.finish(wx_set_error(WX_EHIP, "upload of the class index tables"));
-    int nchunks = pick_chunks(nk, (N + nc - 1) / nc);
-    if ((int64_t)nchunks * nc > 65535) nchunks = 65535 / nc;       // gridDim.y
+    const int nchunks = ldb_chunks(nk, N, nc);
     T *partial = (T *)scr.alloc(sizeof(T) * (size_t)nchunks * nc * nk);
     T *per_sig = (T *)scr.alloc(sizeof(T) * (size_t)N);
     T *den = (T *)scr.alloc(sizeof(T) * 2 * (size_t)nc);
@@ -217,4 +219,12 @@ int wx_class_var_f64(const double *X, int64_t nk, int64_t N, const int32_t *cls,
 { return api_class_reduce<double>(X, nk, 0, N, cls, nc, 2, mean, var, nullptr, stream); }
 int wx_class_var_f32(const float *X, int64_t nk, int64_t N, const int32_t *cls, int nc, const float *mean, float *var, void *stream)
 { return api_class_reduce<float>(X, nk, 0, N, cls, nc, 2, mean, var, nullptr, stream); }
+
+// wx_debug.h: the chunk count api_class_reduce launches with
+int wx_debug_ldb_chunks(int64_t nk, int64_t N, int nc)
+{
+    if (nk < 1 || N < 1 || N >= ((int64_t)1 << 31) || nc < 2 || nc > LDB_MAXC)
+        return wx_set_error(WX_EARG, "wx_debug_ldb_chunks: arguments outside the class reductions' domain");
+    return ldb_chunks(nk, N, nc);
+}
 }
