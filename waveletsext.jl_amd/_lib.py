@@ -56,6 +56,12 @@ def _declare(L):
     L.wx_debug_swt1d_trace_end.restype = _I
     L.wx_debug_swt1d_trace_dropped.argtypes = []
     L.wx_debug_swt1d_trace_dropped.restype = _L
+    L.wx_debug_dwt2d_trace_begin.argtypes = []
+    L.wx_debug_dwt2d_trace_begin.restype = None
+    L.wx_debug_dwt2d_trace_end.argtypes = [_P, _I]
+    L.wx_debug_dwt2d_trace_end.restype = _I
+    L.wx_debug_dwt2d_trace_dropped.argtypes = []
+    L.wx_debug_dwt2d_trace_dropped.restype = _L
     L.wx_debug_swt_inv_plan.argtypes = [_I, _I, _I, _L, _L, _I, _I, _I, _P]
     L.wx_debug_swt_inv_plan.restype = _I
     L.wx_debug_ldb_chunks.argtypes = [_L, _L, _I]
@@ -345,6 +351,39 @@ def swt1d_trace():
         out.dropped = int(L.wx_debug_swt1d_trace_dropped())
         for row in buf[:got].tolist():
             out.append(Swt1dLaunch(SWT1D_ROUTES[row[0]], *row[1:]))
+
+
+# csrc/wx_debug.h: route ids of the 2-D decimated transforms' launch record
+DWT2D_ROUTES = {1: "Q64W", 2: "Q64TPREP", 3: "Q64T", 4: "Q64", 5: "PYR", 6: "TAIL", 7: "L2DF", 8: "L2DC", 9: "COL1D", 10: "LROWS",
+                11: "ROWS", 12: "TILE", 13: "TILEP", 14: "ITILE", 15: "ITILEP", 16: "TWO", 17: "COPYB", 18: "GATHER"}
+DWT2D_TRACE_MAX = 1 << 16
+Dwt2dLaunch = collections.namedtuple("Dwt2dLaunch", "route inverse depth K elem_size block grid_x grid_y grid_z lds e0 e1 e2 e3 e4 e5")
+
+
+class Dwt2dTrace(list):
+    """the list `dwt2d_trace` yields; `dropped` = launches past DWT2D_TRACE_MAX, which the record does not hold"""
+    dropped = 0
+
+
+@contextlib.contextmanager
+def dwt2d_trace():
+    """Record every kernel launch of the 2-D decimated transforms (wpd, wpt, iwpt, iwpd, dwt / idwt of images) made inside the
+    block (csrc/wx_debug.h: wx_debug_dwt2d_trace_begin / _end; process-global, so one block at a time).  Yields a list that
+    holds one Dwt2dLaunch per launch, in launch order, once the block has ended; what e0 .. e5 hold for each route is
+    tabulated in wx_debug.h."""
+    import numpy as np
+    L = lib()
+    out = Dwt2dTrace()
+    L.wx_debug_dwt2d_trace_begin()
+    try:
+        yield out
+    finally:
+        buf = np.empty((DWT2D_TRACE_MAX, len(Dwt2dLaunch._fields)), dtype=np.int32)
+        got = L.wx_debug_dwt2d_trace_end(buf.ctypes.data, DWT2D_TRACE_MAX)
+        check(min(got, 0))
+        out.dropped = int(L.wx_debug_dwt2d_trace_dropped())
+        for row in buf[:got].tolist():
+            out.append(Dwt2dLaunch(DWT2D_ROUTES[row[0]], *row[1:]))
 
 
 def swt_inv_plan(layout, L, F, n, elem_size, sm=None, has_tree=False, haar6=False):

@@ -71,6 +71,44 @@ void wx_debug_swt1d_trace_begin(void);
 int wx_debug_swt1d_trace_end(int32_t *out, int cap);
 int64_t wx_debug_swt1d_trace_dropped(void);
 
+/* Launch record of the 2-D decimated transforms (wpd, wpt, iwpt, iwpd and dwt / idwt of images: wx_api_2d.hip, wx_dwt2d.hip,
+ * wx_lattice_2d64*.h / .hip, wx_lattice_rows.h, wx_lattice2d.h, wx_pyr2d.hip, wx_dwttail.hip): between _begin and _end every
+ * kernel launch of that path appends one row, written next to the launch from the variables the launch uses.  Same protocol
+ * as the 1-D record above: process-global, mutex-protected, one relaxed load of a flag per launch site when disarmed.  The
+ * device-to-device copies (hipMemcpy2DAsync: slice 0 of wpd, depth-0 trees, the inverse without a node list) are not kernels
+ * and are not recorded.  A row is WX_DWT2D_TRACE_FIELDS int32:
+ *     route, inverse, depth, K, elem_size, blockDim.x, gridDim.x, gridDim.y, gridDim.z, dynamic LDS bytes, e0, e1, e2, e3, e4, e5
+ * depth = the depth the pass starts from (forward: the parents' depth; inverse: the children's depth), K = levels in the pass.
+ * NS = lattice stages of the kernel's template instance (wx_lat_stages(F)).  Extras e0 .. (0 where none is named):
+ *     1  Q64W      k_lat2d64_wpd<NS>: wpd of 64 x 64 images, one wavefront each      NS
+ *     2  Q64TPREP  k_lat2d64t_prep: the quad tree's masks and addresses for Q64T
+ *     3  Q64T      k_lat2d64t_f64<NS>: 64 x 64 images along a quad tree              NS
+ *     4  Q64       k_lat2d64_f64<NS>: 64 x 64 images, full tree                      NS
+ *     5  PYR       k_pyr2d_small<T, FT>: whole pyramid of an image in LDS            FT (compile-time taps, 0 = runtime), log2 m, log2 n
+ *     6  TAIL      k_dwt2d_tail<T, F>: the K levels from the 8 x 8 approximation on   F, m   (depth is not known there: 0)
+ *     7  L2DF      k_lat2d_fused_f32<NS, inverse, HB, E>: both passes, one piece     NS, HB, E, units of the piece
+ *                  (a batch of more than 65534 units is as many consecutive L2DF rows as it has pieces)
+ *     8  L2DC      k_lat2d_colT_f32 / _icolT_f32<NS, .., HB>: one transposing pass   NS, HB, pass (1 / 2)
+ *     9  COL1D     the column pass of the fast path: ONE row from the 2-D caller for the call of the 1-D dispatch
+ *                  (wx_dev_wpt1d / wx_dev_iwpt1d; its kernels are not recorded); block, grid and LDS are 0        m, n
+ *    10  LROWS     k_lat_rows_g_f64<NS, 2, SH>: row pass on the lattice kernels      NS, SH, wavefronts per workgroup
+ *    11  ROWS      k_rows_fused<T, F, INVERSE, V, KI, REGL>: row pass in LDS strips  F, V, KI, REGL, strip height R, pitch S
+ *    12  TILE      k_dwt2d_level_tile<T, F>, K = 1 (one row per launch of <= 65535 images)     F, by_node, tree status given, tiles
+ *    13  TILEP     k_dwt2d_level_tile_p<T, F>, persistent, K = 1                     F, by_node, tree status given, tiles
+ *    14  ITILE     k_idwt2d_level_tile<T, F>, K = 1 (one row per launch)             F, by_node, tree status given, tiles
+ *    15  ITILEP    k_idwt2d_level_tile_p<T, F>, persistent, K = 1                    F, by_node, tree status given, tiles
+ *    16  TWO       k_dwt2d_dim1 + k_dwt2d_dim2 (inverse: _dim2 + _dim1), K = 1: ONE row for the pair, which shares a grid
+ *                                                                                    node list given, copy_inactive, tree status given, nodes
+ *    17  COPYB     k_copy_blocks2d, K = 0, depth = first depth below the tile levels nodes
+ *    18  GATHER    k_gather_leaves2d, K = 0, always recorded with inverse = 1: iwpd along a partial tree, and getbasiscoef of an
+ *                  image table (wx_api_swt2d.hip), which shares the launcher     blocks per side, slices k
+ * _end, _dropped and the WX_EARG cases are those of wx_debug_swt1d_trace_end / _dropped. */
+#define WX_DWT2D_TRACE_FIELDS 16
+#define WX_DWT2D_TRACE_MAX (1 << 16)
+void wx_debug_dwt2d_trace_begin(void);
+int wx_debug_dwt2d_trace_end(int32_t *out, int cap);
+int64_t wx_debug_dwt2d_trace_dropped(void);
+
 /* The schedule of the 1-D redundant inverse (wx_swt_inv_plan, the function wx_swt1d's caller runs) under the current dispatch mode;
  * needs no device.  layout 0 / 1 / 2 = dwt / wpt / wpd container, sm < 0 = average based, haar6 = the caller's wx_haar_swpt6_ok.
  * out receives from, to, R, OPT of every pass (4 * L values at most; OPT = 0 marks the Haar register pass, -1 the lane-local one);

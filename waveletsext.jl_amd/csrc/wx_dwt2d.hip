@@ -18,7 +18,11 @@
 #include <type_traits>
 #include "wx_kernels.h"
 #include "wx_host.h"
+#include "wx_dwt2d_trace.h"
+#include "wx_debug.h"
 #include <cstdlib>
+#include <mutex>
+#include <vector>
 
 static __device__ __forceinline__ int64_t wx_quad_heap(int d, int j, int k)
 {
@@ -521,6 +525,8 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     const bool vec = m % VW == 0 && R % VW == 0 && S % VW == 0 && src_img % VW == 0 && dst_img % VW == 0 &&
                      ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && filt.F <= 12;     // 2F-tap window of vectors in registers
     void (*kern)(const T *, T *, int64_t, int64_t, int, int, int, int64_t, WxFilt, int, int, int, int) = nullptr;
+    int kV = 0, kKI = 0, kREGL = 0;                    // the template arguments of `kern`, set where it is chosen (launch record)
+#define WX_ROWS_PICK(FF, VV, KK, RR) (kV = VV, kKI = KK, kREGL = RR, k_rows_fused<T, FF, INVERSE, VV, KK, RR>)
     // in place (one LDS image, two workgroups of 1024 lanes per CU) when a lane has at most two items per level
     // (two workgroups of 512 lanes: the same 16 wavefronts per CU as one workgroup of 1024 with two LDS images,
     // but their load / compute / store phases interleave)
@@ -537,19 +543,20 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     // (64 Float32 columns 1.02 -> 1.34 ms, 64 / 128 Float64 columns 1.04 -> 1.39 ms)
     const bool regl = vec && filt.F <= 8 && ((sizeof(T) == 8 && n >= 256) || n >= 1024);
     switch (filt.F) {
-#define WX_CASE(FF) case FF: kern = vec ? k_rows_fused<T, FF, INVERSE, VW> : k_rows_fused<T, FF, INVERSE, 1>; break;
+#define WX_CASE(FF) case FF: kern = vec ? WX_ROWS_PICK(FF, VW, 0, false) : WX_ROWS_PICK(FF, 1, 0, false); break;
         WX_CASE(10) WX_CASE(12) WX_CASE(14) WX_CASE(16) WX_CASE(18) WX_CASE(20)
 #undef WX_CASE
 #define WX_CASE(FF) case FF:                                                                                                                  \
-        if (regl) kern = inplace ? (items_per_lane <= 1 ? k_rows_fused<T, FF, INVERSE, VW, 1, true> : k_rows_fused<T, FF, INVERSE, VW, 2, true>) \
-                                 : k_rows_fused<T, FF, INVERSE, VW, 0, true>;                                                                 \
-        else kern = inplace ? (items_per_lane <= 1 ? k_rows_fused<T, FF, INVERSE, VW, 1> : k_rows_fused<T, FF, INVERSE, VW, 2>)              \
-                            : (vec ? k_rows_fused<T, FF, INVERSE, VW> : k_rows_fused<T, FF, INVERSE, 1>);                                    \
+        if (regl) kern = inplace ? (items_per_lane <= 1 ? WX_ROWS_PICK(FF, VW, 1, true) : WX_ROWS_PICK(FF, VW, 2, true))                        \
+                                 : WX_ROWS_PICK(FF, VW, 0, true);                                                                             \
+        else kern = inplace ? (items_per_lane <= 1 ? WX_ROWS_PICK(FF, VW, 1, false) : WX_ROWS_PICK(FF, VW, 2, false))                        \
+                            : (vec ? WX_ROWS_PICK(FF, VW, 0, false) : WX_ROWS_PICK(FF, 1, 0, false));                                        \
         break;
         WX_CASE(2) WX_CASE(4) WX_CASE(6) WX_CASE(8)
 #undef WX_CASE
     default: return wx_set_error(WX_EUNSUPPORTED, "no fused row kernel for this filter length");
     }
+#undef WX_ROWS_PICK
     if (lds > 64 * 1024)
         WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -562,6 +569,7 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     while ((1 << (log2R + 1)) <= R) ++log2R;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nt), lds, st, src, dst, src_img, dst_img, (int)m, log2n, L, batch,
                        filt, log2R, S, 1, regl ? 1 : 0);
+    WX_DWT2D_TRACE(WX_R2_ROWS, INVERSE, INVERSE ? L : 0, L, sizeof(T), dim3((unsigned)grid), dim3(nt), lds, filt.F, kV, kKI, kREGL, R, S);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
 }
@@ -616,10 +624,12 @@ int wx_dev_wpt2d_fast(const T *x, T *y, int64_t m, int64_t n, int L, int64_t bat
     }
     if (!inverse) {
         // columns: the images' columns are m-sample signals, contiguous: (m, n*batch)
+        WX_DWT2D_TRACE(WX_R2_COL1D, 0, 0, L, sizeof(T), dim3(0, 0, 0), dim3(0), 0, (int)m, (int)n);
         if ((rc = wx_dev_wpt1d<T>(x, tmp, m, L, n * batch, filt, nullptr, 0, nullptr, st, 0))) return rc;
         if ((rc = wx_launch_rows<T, false>(tmp, y, mn, mn, m, n, L, batch, filt, st))) return rc;
     } else {
         if ((rc = wx_launch_rows<T, true>(x, tmp, in_img, mn, m, n, L, batch, filt, st))) return rc;
+        WX_DWT2D_TRACE(WX_R2_COL1D, 1, L, L, sizeof(T), dim3(0, 0, 0), dim3(0), 0, (int)m, (int)n);
         if ((rc = wx_dev_iwpt1d<T>(tmp, y, m, L, n * batch, filt, nullptr, 0, nullptr, 0, m, nullptr, nullptr, st, 0))) return rc;
     }
     return WX_OK;
@@ -979,6 +989,7 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
         if (grid > total) grid = total;
         hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(256), lds, st, src, dst, src_img, dst_img, m, n, d, filt, di, tt.int_img, tt.status,
                            tt.nstatus, by_node ? tt.act : (const int *)nullptr, tiles, total);
+        WX_DWT2D_TRACE(WX_R2_TILEP, 0, d, 1, sizeof(T), dim3((unsigned)grid), dim3(256), lds, F, by_node ? 1 : 0, tt.status ? 1 : 0, (int)tiles);
         return true;
     }
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
@@ -986,6 +997,7 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
         hipLaunchKernelGGL(kern, dim3(tiles, bc), dim3(256), lds, st, src + b0 * src_img, dst + b0 * dst_img, src_img,
                            dst_img, m, n, d, filt, di ? di + b0 * tt.int_img : (T *)nullptr, tt.int_img, tt.status,
                            tt.nstatus, by_node ? tt.act : (const int *)nullptr);
+        WX_DWT2D_TRACE(WX_R2_TILE, 0, d, 1, sizeof(T), dim3(tiles, bc), dim3(256), lds, F, by_node ? 1 : 0, tt.status ? 1 : 0, (int)tiles);
     }
     return true;
 }
@@ -1359,6 +1371,7 @@ static bool wx_launch_ilevel_tile_F(const T *src_leaf, int64_t leaf_img, const T
         if (grid > total) grid = total;
         hipLaunchKernelGGL(kp, dim3((unsigned)grid), dim3(256), lds, st, src_leaf, leaf_img, src_int, tt.int_img, dst, dst_img, m, n, d, filt,
                            tt.status, tt.nstatus, tt.act, tiles, total);
+        WX_DWT2D_TRACE(WX_R2_ITILEP, 1, d + 1, 1, sizeof(T), dim3((unsigned)grid), dim3(256), lds, F, by_node ? 1 : 0, tt.status ? 1 : 0, (int)tiles);
         return true;
     }
     for (int64_t b0 = 0; b0 < batch; b0 += 65535) {
@@ -1366,6 +1379,7 @@ static bool wx_launch_ilevel_tile_F(const T *src_leaf, int64_t leaf_img, const T
         hipLaunchKernelGGL(kern, dim3(tiles, bc), dim3(256), lds, st, src_leaf + b0 * leaf_img, leaf_img,
                            src_int ? src_int + b0 * tt.int_img : (const T *)nullptr, tt.int_img, dst + b0 * dst_img, dst_img,
                            m, n, d, filt, tt.status, tt.nstatus, by_node ? tt.act : (const int *)nullptr);
+        WX_DWT2D_TRACE(WX_R2_ITILE, 1, d + 1, 1, sizeof(T), dim3(tiles, bc), dim3(256), lds, F, by_node ? 1 : 0, tt.status ? 1 : 0, (int)tiles);
     }
     return true;
 }
@@ -1412,6 +1426,8 @@ static void wx_launch_level2d(const T *src, T *tmp, T *dst, int64_t src_img, int
         hipLaunchKernelGGL((k_dwt2d_dim1<T, true>), dim3(g), dim3(256), 0, st, (const T *)tmp, dst, mn, dst_img, m, n,
                            d, batch, filt, status, nstatus, copy_inactive, act, nact);
     }
+    // (one row for the pair: both launches have this grid)
+    WX_DWT2D_TRACE(WX_R2_TWO, INVERSE, INVERSE ? d + 1 : d, 1, sizeof(T), dim3(g), dim3(256), 0, act ? 1 : 0, copy_inactive, status ? 1 : 0, nact);
 }
 
 // wpd 2-D: y is (m, n, L+1, batch); tmp holds m*n*batch elements
@@ -1545,6 +1561,7 @@ int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
                 const int64_t tot = (int64_t)(m >> Lt) * (n >> Lt) * nact[(size_t)Lt] * batch;
                 hipLaunchKernelGGL(k_copy_blocks2d<T>, dim3(wx_grid2(tot)), dim3(256), 0, st, x, B, in_img, mn, (int)m, Lt, batch,
                                    dact[(size_t)Lt], nact[(size_t)Lt], (int)n);
+                WX_DWT2D_TRACE(WX_R2_COPYB, 1, Lt, 0, sizeof(T), dim3(wx_grid2(tot)), dim3(256), 0, nact[(size_t)Lt]);
                 for (int d = L - 1; d >= Lt; --d) level2(B, mn, B, sc[(Lt + 1) & 1], d, true);
             }
             for (int d = Lt - 1; d >= 0; --d) {
@@ -1594,6 +1611,7 @@ int wx_dev_gather_leaves2d(const T *Xw, T *out, int64_t m, int64_t n, int k, int
     if (batch == 0 || m * n == 0) return WX_OK;
     hipLaunchKernelGGL(k_gather_leaves2d<T>, dim3(wx_grid2(batch * m * n)), dim3(256), 0, st, Xw, out, (int)m, (int)n,
                        k, batch, colmap, nblk, (int)(m / nblk), (int)(n / nblk));
+    WX_DWT2D_TRACE(WX_R2_GATHER, 1, 0, 0, sizeof(T), dim3(wx_grid2(batch * m * n)), dim3(256), 0, nblk, k);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
 }
@@ -1607,3 +1625,49 @@ int wx_dev_gather_leaves2d(const T *Xw, T *out, int64_t m, int64_t n, int k, int
     template int wx_dev_wpt2d_fast<T>(const T *, T *, int64_t, int64_t, int, int64_t, const WxFilt &, T *, bool, int64_t, hipStream_t);
 WX_INST(double)
 WX_INST(float)
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// launch record of the parity suite (wx_debug.h; rows appended by WX_DWT2D_TRACE, wx_dwt2d_trace.h)
+// ---------------------------------------------------------------------------------------------------------------------------------
+std::atomic<int> wx_dwt2d_trace_armed{0};
+static std::mutex g_dwt2d_trace_mu;                      // test_gpu_stress.py calls the library from several threads
+static std::vector<int32_t> g_dwt2d_trace_rows;
+static int64_t g_dwt2d_trace_dropped = 0;
+
+void wx_dwt2d_trace_add(int route, int inverse, int depth, int K, size_t esz, dim3 grid, dim3 block, size_t lds, int e0, int e1, int e2,
+                        int e3, int e4, int e5)
+{
+    std::lock_guard<std::mutex> lk(g_dwt2d_trace_mu);
+    if (!wx_dwt2d_trace_armed.load(std::memory_order_relaxed)) return;
+    if (g_dwt2d_trace_rows.size() >= (size_t)WX_DWT2D_TRACE_MAX * WX_DWT2D_TRACE_FIELDS) { ++g_dwt2d_trace_dropped; return; }
+    const int32_t row[WX_DWT2D_TRACE_FIELDS] = {route, inverse ? 1 : 0, depth, K, (int32_t)esz, (int32_t)block.x, (int32_t)grid.x, (int32_t)grid.y,
+                                                (int32_t)grid.z, (int32_t)lds, e0, e1, e2, e3, e4, e5};
+    g_dwt2d_trace_rows.insert(g_dwt2d_trace_rows.end(), row, row + WX_DWT2D_TRACE_FIELDS);
+}
+
+extern "C" void wx_debug_dwt2d_trace_begin(void)
+{
+    std::lock_guard<std::mutex> lk(g_dwt2d_trace_mu);
+    g_dwt2d_trace_rows.clear();
+    g_dwt2d_trace_dropped = 0;
+    wx_dwt2d_trace_armed.store(1);
+}
+
+extern "C" int wx_debug_dwt2d_trace_end(int32_t *out, int cap)
+{
+    std::lock_guard<std::mutex> lk(g_dwt2d_trace_mu);
+    if (!out || cap <= 0) return wx_set_error(WX_EARG, "wx_debug_dwt2d_trace_end: no room for a single entry");
+    if (!wx_dwt2d_trace_armed.load()) return wx_set_error(WX_EARG, "wx_debug_dwt2d_trace_end without wx_debug_dwt2d_trace_begin");
+    wx_dwt2d_trace_armed.store(0);
+    const size_t rows = g_dwt2d_trace_rows.size() / WX_DWT2D_TRACE_FIELDS;
+    const size_t ncopy = rows < (size_t)cap ? rows : (size_t)cap;
+    for (size_t i = 0; i < ncopy * WX_DWT2D_TRACE_FIELDS; ++i) out[i] = g_dwt2d_trace_rows[i];
+    std::vector<int32_t>().swap(g_dwt2d_trace_rows);
+    return (int)rows;
+}
+
+extern "C" int64_t wx_debug_dwt2d_trace_dropped(void)
+{
+    std::lock_guard<std::mutex> lk(g_dwt2d_trace_mu);
+    return g_dwt2d_trace_dropped;
+}

@@ -13,6 +13,7 @@
 #include "wx_common.h"
 #include "wx_kernels.h"
 #include "wx_host.h"
+#include "wx_dwt2d_trace.h"
 #include <cstdlib>
 
 namespace {
@@ -187,6 +188,8 @@ int wx_dwt2d_tail(T *y, int64_t m, int Lt, int64_t batch, const WxFilt &filt, hi
         default: return wx_set_error(WX_EHIP, "dwt 2-D tail: unsupported filter length");
     }
     hipLaunchKernelGGL(k, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, y, m, batch, Lt, filt);
+    // (the tail starts at the 8 x 8 approximation, whatever depth that is: the record keeps the side m instead of a depth)
+    WX_DWT2D_TRACE(WX_R2_TAIL, 0, 0, Lt, sizeof(T), dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, filt.F, (int)m);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
 }

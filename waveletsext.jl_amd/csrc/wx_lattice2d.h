@@ -28,6 +28,7 @@
 // lanes (quad_perm).  Depth 6 needs levels on index bits 0..5 only: A takes 0-1, B takes 2-5.
 #include "wx_common.h"
 #include "wx_kernels.h"
+#include "wx_dwt2d_trace.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -1068,6 +1069,7 @@ static int wx_lattice2d_fused_launch(const float *src, float *dst, float *ring, 
     default: return 0;
     }
 #undef WX_GO2F
+    WX_DWT2D_TRACE(WX_R2_L2DF, inverse, inverse ? L : 0, L, sizeof(float), grid, wg, 0, wx_lat_stages(filt.F), HB, hc.mm.e ? 1 : 0, fz.units);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice2d fused launch", __FILE__, __LINE__);
     return 1;
@@ -1112,6 +1114,7 @@ static int wx_lattice2d_launch(const float *src, float *dst, int64_t m, int L, i
     }
 #undef WX_GO2
 #undef WX_GO2K
+    WX_DWT2D_TRACE(WX_R2_L2DC, inverse, inverse ? L : 0, L, sizeof(float), grid, wg, 0, nsq, HB, pass);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice2d launch", __FILE__, __LINE__);
     return 1;

@@ -12,6 +12,7 @@
 // Until round 5 these images took the generic two-pass path (a column kernel and a row kernel through an intermediate image in HBM:
 // 0.24-0.27 of the roofline of the one-pass byte count).
 #include "wx_lattice_dev.h"
+#include "wx_dwt2d_trace.h"
 
 template <int NS, int WPE, typename IO, bool INV>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void k_lat2d64_f64(
@@ -129,6 +130,7 @@ static int wx_lattice_2d64_launch(const IO *x, IO *y, int L, int64_t batch, int6
             return 0;
     }
 #undef WX_GO2
+    WX_DWT2D_TRACE(WX_R2_Q64, INV, INV ? L : 0, L, sizeof(IO), dim3(pp.nwave), dim3(64), 0, wx_lat_stages(filt.F));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice 2-D launch (64 x 64 images)", __FILE__, __LINE__);
     return 1;

@@ -15,6 +15,7 @@
 // column branch is register bit 0 of layout C) and streams it out with 16-byte-per-lane stores.  The inverse mirrors it.
 // Cost next to the full-tree kernel: 4 exchanges per level instead of 2 per transform -- the kernel is LDS-issue bound, not FP64 bound.
 #include "wx_lattice_dev.h"
+#include "wx_dwt2d_trace.h"
 #include "wx_host.h"
 #include "wx_lattice_tree_sc.h"
 
@@ -222,6 +223,7 @@ static int wx_lattice_2d64t_launch(const IO *x, IO *y, int L, int64_t batch, int
     WxLat2dTree *tab = (WxLat2dTree *)scr.alloc(sizeof(WxLat2dTree));
     if (!tab) return WX_EHIP;
     hipLaunchKernelGGL(k_lat2d64t_prep, dim3(1), dim3(256), 0, st, dstatus, nstatus, L, tab);
+    WX_DWT2D_TRACE(WX_R2_Q64TPREP, INV, INV ? L : 0, L, sizeof(IO), dim3(1), dim3(256), 0);
     const WxLat2dTree *ctab = tab;
 #define WX_GOQ(NSS)                                                                                                                  \
     case NSS:                                                                                                                        \
@@ -239,6 +241,7 @@ static int wx_lattice_2d64t_launch(const IO *x, IO *y, int L, int64_t batch, int
             return 0;
     }
 #undef WX_GOQ
+    WX_DWT2D_TRACE(WX_R2_Q64T, INV, INV ? L : 0, L, sizeof(IO), dim3(pp.nwave), dim3(64), 0, wx_lat_stages(filt.F));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice 2-D quad-tree launch (64 x 64 images)", __FILE__, __LINE__);
     return 1;

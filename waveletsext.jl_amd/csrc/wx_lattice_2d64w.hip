@@ -6,6 +6,7 @@
 // 64 + 64 live 8-byte registers and the exchange temporaries: one wavefront per SIMD (512 registers); the kernel is a stream of
 // (L + 1) x 32 KiB stores per 32 KiB load, which is what bounds it.
 #include "wx_lattice_dev.h"
+#include "wx_dwt2d_trace.h"
 
 namespace {
 
@@ -75,6 +76,7 @@ int wx_lattice_2d64_wpd_T(const IO *x, IO *y, int L, int64_t batch, const WxFilt
     default: return 0;
     }
 #undef WX_GOW
+    WX_DWT2D_TRACE(WX_R2_Q64W, 0, 0, L, sizeof(IO), dim3(pp.nwave), dim3(64), 0, wx_lat_stages(filt.F));
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice 2-D wpd launch (64 x 64 images)", __FILE__, __LINE__);
     return 1;

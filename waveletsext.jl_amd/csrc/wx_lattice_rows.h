@@ -12,6 +12,7 @@
 // wx_dwt2d.hip: LDS-issue bound).  Measured per GiB, column pass + row pass, db4 (profiles/r05_floor2d.txt): 128 x 128 Float64 full depth
 // 1.13 -> 0.80 ms, 256 x 256 Float64 1.08 -> 0.85 ms, 128 x 128 Float32 1.25 -> 0.95 ms; Float32 at depth 3 no gain (not taken below 5).
 #include "wx_lattice_dev.h"
+#include "wx_dwt2d_trace.h"
 
 // W wavefronts per workgroup (512 columns: 2, 1024 columns: 4): they take ADJACENT row groups, so that the 64- / 32-byte runs of a wavefront
 // are halves / quarters of 128-byte lines the workgroup's other wavefronts ask for at about the same time on the same CU
@@ -79,6 +80,7 @@ static int wx_lattice_rows_launch(const IO *x, IO *y, int64_t in_img, int64_t ou
             return 0;
     }
 #undef WX_GOR
+    WX_DWT2D_TRACE(WX_R2_LROWS, INV, INV ? L : 0, L, sizeof(IO), dim3((unsigned)(nwave / W)), dim3(64 * W), 0, wx_lat_stages(filt.F), SH, W);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice row pass launch", __FILE__, __LINE__);
     return 1;

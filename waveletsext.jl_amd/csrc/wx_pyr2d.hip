@@ -9,6 +9,7 @@
 #include "wx_common.h"
 #include "wx_kernels.h"
 #include "wx_host.h"
+#include "wx_dwt2d_trace.h"
 
 namespace {
 
@@ -165,6 +166,7 @@ int launch(bool inverse, const T *x, T *y, int lm, int ln, int L, int64_t batch,
     if (grid > batch) grid = batch;
     if (inverse) hipLaunchKernelGGL(ki, dim3((unsigned)grid), dim3(nt), lds, st, x, y, lm, ln, L, batch, filt);
     else hipLaunchKernelGGL(kf, dim3((unsigned)grid), dim3(nt), lds, st, x, y, lm, ln, L, batch, filt);
+    WX_DWT2D_TRACE(WX_R2_PYR, inverse, inverse ? L : 0, L, sizeof(T), dim3((unsigned)grid), dim3(nt), lds, FT, lm, ln);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "small-image pyramid launch", __FILE__, __LINE__);
     return WX_OK;
