@@ -274,6 +274,31 @@ def test_dwt2d_debug_entry_points_refuse_bad_arguments(wx):
     assert len(wx.Dwt2dLaunch._fields) == 16                                    # WX_DWT2D_TRACE_FIELDS
 
 
+def test_dwt1d_debug_entry_points_refuse_bad_arguments(wx):
+    """csrc/wx_debug.h: the launch record of the 1-D decimated transforms, at the C level (no device): the protocol of the other records"""
+    lib = ctypes.CDLL(wx.LIB_PATH)
+    EARG = -2
+    i64, ci = ctypes.c_int64, ctypes.c_int
+    lib.wx_debug_dwt1d_trace_dropped.restype = i64
+    row = (ctypes.c_int32 * 16)()
+    assert lib.wx_debug_dwt1d_trace_end(row, ci(1)) == EARG                     # end without begin
+    lib.wx_debug_dwt1d_trace_begin()
+    assert lib.wx_debug_dwt1d_trace_end(row, ci(0)) == EARG                     # cap = 0: refused, the record stays armed
+    assert lib.wx_debug_dwt1d_trace_end(row, ci(-1)) == EARG
+    assert lib.wx_debug_dwt1d_trace_end(None, ci(4)) == EARG                    # NULL output pointer: refused, still armed
+    assert lib.wx_debug_dwt1d_trace_end(row, ci(1)) == 0                        # an empty record: nothing was launched
+    assert lib.wx_debug_dwt1d_trace_dropped() == 0
+    assert lib.wx_debug_dwt1d_trace_end(row, ci(1)) == EARG                     # that end disarmed it
+    with wx.dwt1d_trace() as tr:
+        pass
+    assert list(tr) == [] and tr.dropped == 0
+    with wx.dwt1d_trace() as tr, wx.dwt2d_trace() as tr2, wx.swt1d_trace() as tr1:   # the three records are independent
+        pass
+    assert list(tr) == [] and list(tr2) == [] and list(tr1) == []
+    assert set(wx.DWT1D_ROUTES) == set(range(1, 19)) and len(set(wx.DWT1D_ROUTES.values())) == 18
+    assert len(wx.Dwt1dLaunch._fields) == 16                                    # WX_DWT1D_TRACE_FIELDS
+
+
 def test_header_compiles_as_c_and_example_links(tmp_path, wx):
     """include/waveletsext_hip.h is a C header: examples/roundtrip.c builds with gcc -std=c99 against the .so
     (and, without a GPU, fails loudly with the library's status instead of computing on the CPU)"""

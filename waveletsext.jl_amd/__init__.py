@@ -13,7 +13,7 @@ from .util import (maxtransformlevels, isdyadic, ndyadicscales, nodelength, getc
                    getrowrange, getcolrange, main2depthshift, coarsestscalingrange,
                    finestdetailrange, delete_subtree)
 from ._arrays import jl_empty, to_device, to_numpy, to_colmajor                     # noqa: F401
-from ._lib import WxError, build_info, device_count, dwt2d_trace, lattice_factor, lattice_fold_matrix, ldb_chunks, red2d_route, set_force_generic, set_host_hugepages, shutdown, swt1d_trace, swt_inv_plan, wpt_trees_route, LIB_PATH, DWT2D_ROUTES, Dwt2dLaunch, RED2D_ROUTES, SWT1D_ROUTES, WPT_TREES_ROUTES                # noqa: F401
+from ._lib import WxError, build_info, device_count, dwt1d_trace, dwt2d_trace, lattice_factor, lattice_fold_matrix, ldb_chunks, red2d_route, set_force_generic, set_host_hugepages, shutdown, swt1d_trace, swt_inv_plan, wpt_trees_route, LIB_PATH, DWT1D_ROUTES, DWT2D_ROUTES, Dwt1dLaunch, Dwt2dLaunch, RED2D_ROUTES, SWT1D_ROUTES, WPT_TREES_ROUTES                # noqa: F401
 from .dwt import (wpd, wpd_, wpdall, iwpd, iwpd_, iwpdall, wpt, wpt_, iwpt, iwpt_,   # noqa: F401
                   wptall, iwptall, getbasiscoef, getbasiscoefall, dwt, idwt, dwtall, idwtall)
 from .swt import (sdwt, sdwt_, sdwtall, isdwt, isdwt_, isdwtall, swpt, swpt_, swptall, iswpt, iswpt_,   # noqa: F401

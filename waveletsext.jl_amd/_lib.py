@@ -62,6 +62,12 @@ def _declare(L):
     L.wx_debug_dwt2d_trace_end.restype = _I
     L.wx_debug_dwt2d_trace_dropped.argtypes = []
     L.wx_debug_dwt2d_trace_dropped.restype = _L
+    L.wx_debug_dwt1d_trace_begin.argtypes = []
+    L.wx_debug_dwt1d_trace_begin.restype = None
+    L.wx_debug_dwt1d_trace_end.argtypes = [_P, _I]
+    L.wx_debug_dwt1d_trace_end.restype = _I
+    L.wx_debug_dwt1d_trace_dropped.argtypes = []
+    L.wx_debug_dwt1d_trace_dropped.restype = _L
     L.wx_debug_swt_inv_plan.argtypes = [_I, _I, _I, _L, _L, _I, _I, _I, _P]
     L.wx_debug_swt_inv_plan.restype = _I
     L.wx_debug_ldb_chunks.argtypes = [_L, _L, _I]
@@ -384,6 +390,39 @@ def dwt2d_trace():
         out.dropped = int(L.wx_debug_dwt2d_trace_dropped())
         for row in buf[:got].tolist():
             out.append(Dwt2dLaunch(DWT2D_ROUTES[row[0]], *row[1:]))
+
+
+# csrc/wx_debug.h: route ids of the 1-D decimated transforms' launch record
+DWT1D_ROUTES = {1: "LATF64", 2: "LATWPD", 3: "LATF32", 4: "LATTREE", 5: "LAT8KT", 6: "LANETREE", 7: "SMALLTREE", 8: "HAAR", 9: "TOP",
+                10: "TOPWPD", 11: "FUSED", 12: "L1TILE", 13: "LEVEL", 14: "GATHER", 15: "TAIL", 16: "ITAIL", 17: "THRFUSED", 18: "THRCOPY"}
+DWT1D_TRACE_MAX = 1 << 16
+Dwt1dLaunch = collections.namedtuple("Dwt1dLaunch", "route inverse elem_size n depth K signals F e0 e1 e2 e3 e4 block grid lds")
+
+
+class Dwt1dTrace(list):
+    """the list `dwt1d_trace` yields; `dropped` = launches past DWT1D_TRACE_MAX, which the record does not hold"""
+    dropped = 0
+
+
+@contextlib.contextmanager
+def dwt1d_trace():
+    """Record every kernel launch of the 1-D decimated transforms (wpd, wpt, iwpt, iwpd, dwt / idwt of signals, the thresholded
+    inverse behind denoise) made inside the block (csrc/wx_debug.h: wx_debug_dwt1d_trace_begin / _end; process-global, so one
+    block at a time).  Yields a list that holds one Dwt1dLaunch per launch, in launch order, once the block has ended; what
+    e0 .. e4 hold for each route is tabulated in wx_debug.h."""
+    import numpy as np
+    L = lib()
+    out = Dwt1dTrace()
+    L.wx_debug_dwt1d_trace_begin()
+    try:
+        yield out
+    finally:
+        buf = np.empty((DWT1D_TRACE_MAX, len(Dwt1dLaunch._fields)), dtype=np.int32)
+        got = L.wx_debug_dwt1d_trace_end(buf.ctypes.data, DWT1D_TRACE_MAX)
+        check(min(got, 0))
+        out.dropped = int(L.wx_debug_dwt1d_trace_dropped())
+        for row in buf[:got].tolist():
+            out.append(Dwt1dLaunch(DWT1D_ROUTES[row[0]], *row[1:]))
 
 
 def swt_inv_plan(layout, L, F, n, elem_size, sm=None, has_tree=False, haar6=False):

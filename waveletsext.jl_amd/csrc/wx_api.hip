@@ -6,6 +6,7 @@
 #include "wx_kernels.h"
 #include "wx_lanetree.h"
 #include "wx_lattice_dn_api.h"
+#include "wx_dwt1d_trace.h"
 #include <atomic>
 #include <cstring>
 
@@ -165,6 +166,7 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
         // Float32 full trees of 64 .. 2048 samples: the interleaved lattice kernels where they apply (wx_lattice_sg32.h)
         if (small && tr.full && !f32_full_as_tree && tr.Leff >= 1 && batch && dx != dy && !wx_skip_register_kernels()) {
             const int r = wx_lattice_f32(INVERSE, (const float *)dx, (float *)dy, n, tr.Leff, batch, n, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, INVERSE, sizeof(T), n, INVERSE ? tr.Leff : 0, tr.Leff, batch, F, wx_lat_stages(F), 0, 0);
             if (r) return io.finish(r < 0 ? r : WX_OK);
         }
     }
@@ -189,6 +191,7 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
                 r = wx_lattice_tree_f64(INVERSE, (const double *)dx, (double *)dy, n, tr.Leff, batch, n, 0, filt, ds, ns, st, nullptr, 0);
             else
                 r = wx_lattice_tree_f32(INVERSE, (const float *)dx, (float *)dy, n, tr.Leff, batch, n, filt, ds, ns, st, nullptr, 0);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, INVERSE, sizeof(T), n, INVERSE ? tr.Leff : 0, tr.Leff, batch, F, tr.full, 0, 0, 0, 0);
         }
         if (r) return io.finish(r < 0 ? r : WX_OK);
     }
@@ -200,11 +203,13 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
             const int64_t nn = ((int64_t)1 << tr.Leff) - 1;
             for (int64_t h = 0; h < nn; ++h)
                 if (tr.full || (h < ntree && tree[h])) lt.bits[h >> 5] |= 1u << (h & 31);
+            WX_DWT1D_TRACE(WX_R1_LANETREE, INVERSE, sizeof(T), n, INVERSE ? tr.Leff : 0, tr.Leff, batch, F, tr.full);
             if constexpr (sizeof(T) == 8)
                 return io.finish(wx_lane_tree_f64(INVERSE, (const double *)dx, (double *)dy, n, tr.Leff, batch, lt, filt, st));
             else
                 return io.finish(wx_lane_tree_f32(INVERSE, (const float *)dx, (float *)dy, n, tr.Leff, batch, lt, filt, st));
         }
+        WX_DWT1D_TRACE(WX_R1_SMALLTREE, INVERSE, sizeof(T), n, INVERSE ? tr.Leff : 0, tr.Leff, batch, F, tr.dstatus != nullptr);
         return io.finish(wx_dev_small_tree<T>(INVERSE, dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, st));
     }
     T *s1 = nullptr;
@@ -213,7 +218,8 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
     const bool long_lattice = !force && !tr.dstatus && n > 4096 && n <= 65536 && tr.Leff > 1;
     // any other tree on a long Float64 signal: tiled top levels node by node + one lattice launch per 4096-sample subtree
     const bool longt = !longp && tree && tr.dstatus && tr.Leff >= 1 && !force && wx_wpt_long_tree_ok<T>(n, filt) && dx != dy;
-    if (((!fused && tr.Leff > 1) || long_lattice || longp || longt) && batch) {
+    // (in place the per-level kernels read a copy of the input where their first level would land in the array it reads: dx == dy)
+    if (((!fused && (tr.Leff > 1 || (tr.Leff == 1 && dx == dy))) || long_lattice || longp || longt) && batch) {
         s1 = (T *)scr.alloc(sizeof(T) * n * batch);
         if (!s1) return io.finish(WX_EHIP);
     }
@@ -224,12 +230,14 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
             if (tail) {
                 T *head = (T *)scr.alloc(sizeof(T) * 64 * batch);
                 if (!head) return io.finish(WX_EHIP);
+                WX_DWT1D_TRACE(WX_R1_ITAIL, 1, sizeof(T), n, tr.Leff + tail, tail, batch, F, tail, 0);
                 if ((rc = wx_idwt_tail<T>(dx, head, n, tail, batch, filt, thr, st))) return io.finish(rc);
                 thr.head = head;
             }
             rc = wx_dev_idwt_long<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, thr, s1, st);
         } else {
             rc = wx_dev_dwt_long<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, s1, st);
+            if (rc == WX_OK && tail) WX_DWT1D_TRACE(WX_R1_TAIL, 0, sizeof(T), n, tr.Leff, tail, batch, F, tail, 0);
             if (rc == WX_OK && tail) rc = wx_dwt_tail<T>(dy, n, tail, batch, filt, st);
         }
         return io.finish(rc);
@@ -238,13 +246,16 @@ static int api_wpt1d(const T *x, T *y, int64_t n, int L, const uint8_t *tree, in
         T *head = (T *)scr.alloc(sizeof(T) * 64 * batch);
         if (!head) return io.finish(WX_EHIP);
         WxThreshArg thr{nullptr, 0, 0, 0, 1.0};
+        WX_DWT1D_TRACE(WX_R1_ITAIL, 1, sizeof(T), n, tr.Leff + tail, tail, batch, F, tail, 0);
         rc = wx_idwt_tail<T>(dx, head, n, tail, batch, filt, thr, st);
         thr.head = head;
+        if (rc == WX_OK) WX_DWT1D_TRACE(WX_R1_THRFUSED, 1, sizeof(T), n, tr.Leff, tr.Leff, batch, F, 0, 0, 1);
         if (rc == WX_OK) rc = wx_dev_iwpt1d_thresh<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, thr, st);
     } else if (INVERSE)
         rc = wx_dev_iwpt1d<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, nullptr, 0, n, s1, nullptr, st, force);
     else
         rc = wx_dev_wpt1d<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, s1, st, force);
+    if (rc == WX_OK && tail && !INVERSE) WX_DWT1D_TRACE(WX_R1_TAIL, 0, sizeof(T), n, tr.Leff, tail, batch, F, tail, 0);
     if (rc == WX_OK && tail && !INVERSE) rc = wx_dwt_tail<T>(dy, n, tail, batch, filt, st);
     return io.finish(rc);
 }
@@ -290,15 +301,18 @@ static int api_iwpt1d_thresh(const T *x, T *y, int64_t n, int L, const uint8_t *
         if (tail) {
             T *head = (T *)scr.alloc(sizeof(T) * 64 * batch);
             if (!head) return io.finish(WX_EHIP);
+            WX_DWT1D_TRACE(WX_R1_ITAIL, 1, sizeof(T), n, tr.Leff + tail, tail, batch, F, tail, 1);
             if ((rc = wx_idwt_tail<T>(dx, head, n, tail, batch, filt, thr, st))) return io.finish(rc);
             thr.head = head;
         }
+        WX_DWT1D_TRACE(WX_R1_THRFUSED, 1, sizeof(T), n, tr.Leff, tr.Leff, batch, F, th_kind, per, thr.head != nullptr, row_lo > 0);
         return io.finish(wx_dev_iwpt1d_thresh<T>(dx, dy, n, tr.Leff, batch, filt, tr.dstatus, tr.nstatus, thr, st));
     }
     if (tail) return io.finish(wx_set_error(WX_EHIP, "iwpt: inconsistent pyramid plan"));
     // other kernels (full trees on the lattice, long signals, L = 0): threshold into a scratch copy, then the inverse
     T *xt = (T *)scr.alloc(sizeof(T) * n * batch);
     if (!xt) return io.finish(WX_EHIP);
+    WX_DWT1D_TRACE(WX_R1_THRCOPY, 1, sizeof(T), n, tr.Leff, 0, batch, F, th_kind, per, 0, row_lo > 0);
     if ((rc = wx_dev_threshold_copy<T>(dx, xt, n, batch, th_kind, dt, per, row_lo, scale, st))) return io.finish(rc);
     const int force = wx_force_generic();
     T *s1 = nullptr;

@@ -90,7 +90,8 @@ int64_t wx_debug_swt1d_trace_dropped(void);
  *                  (a batch of more than 65534 units is as many consecutive L2DF rows as it has pieces)
  *     8  L2DC      k_lat2d_colT_f32 / _icolT_f32<NS, .., HB>: one transposing pass   NS, HB, pass (1 / 2)
  *     9  COL1D     the column pass of the fast path: ONE row from the 2-D caller for the call of the 1-D dispatch
- *                  (wx_dev_wpt1d / wx_dev_iwpt1d; its kernels are not recorded); block, grid and LDS are 0        m, n
+ *                  (wx_dev_wpt1d / wx_dev_iwpt1d; its kernels appear in the 1-D record below when that one is armed, not
+ *                  here); block, grid and LDS are 0                                  m, n
  *    10  LROWS     k_lat_rows_g_f64<NS, 2, SH>: row pass on the lattice kernels      NS, SH, wavefronts per workgroup
  *    11  ROWS      k_rows_fused<T, F, INVERSE, V, KI, REGL>: row pass in LDS strips  F, V, KI, REGL, strip height R, pitch S
  *    12  TILE      k_dwt2d_level_tile<T, F>, K = 1 (one row per launch of <= 65535 images)     F, by_node, tree status given, tiles
@@ -108,6 +109,51 @@ int64_t wx_debug_swt1d_trace_dropped(void);
 void wx_debug_dwt2d_trace_begin(void);
 int wx_debug_dwt2d_trace_end(int32_t *out, int cap);
 int64_t wx_debug_dwt2d_trace_dropped(void);
+
+/* Launch record of the 1-D decimated transforms (wpd, wpt, iwpt, iwpd, dwt / idwt of signals, the thresholded inverse behind
+ * denoise: wx_api.hip, wx_dwt1d.hip and the launchers they call): between _begin and _end every kernel launch of that dispatch
+ * appends one row.  A hook sits in the caller, next to the call, and is written from the variables the call uses: a launcher that
+ * answers 0 = declined / 1 = launched is recorded when it answers 1, one that always launches just before the call.  The kernels
+ * wx_dwt1d.hip launches itself (FUSED, L1TILE, LEVEL, GATHER) record in their launchers, with block, grid and dynamic LDS; those are 0
+ * for the other routes.  Same protocol as the records above: process-global, mutex-protected, one relaxed load of a flag per site when
+ * disarmed.  Device-to-device copies (hipMemcpy*Async: L = 0, slice 0 of wpd, the densifying copies of iwpd, leaves of long trees)
+ * are not kernels and are not recorded; the one-pass kernels of denoiseall (wx_lattice_denoise*_f64) are not recorded either.  The
+ * column pass of the 2-D fast path (COL1D above) and the per-signal-tree entries call the same dispatch and show up here.
+ * A row is WX_DWT1D_TRACE_FIELDS int32:
+ *     route, inverse, elem_size, n, depth, K, signals, F, e0, e1, e2, e3, e4, blockDim.x, gridDim.x, dynamic LDS bytes
+ * n and signals are what the launcher was given (the node length and batch << d0 for sub-signal launches; signals clamped to
+ * 2^31 - 1), depth = the depth the pass starts from (forward: the parents' depth; inverse: the deepest children's depth), K = levels
+ * in the pass, F = filter length.  Extras e0 .. e4 (0 where none is named):
+ *     1  LATF64     wx_lattice_wpt_f64 / _iwpt_f64 (n, L fix the kernel: _g 64 .. 512, _sh 1024 / 2048, _lo 4096 at L <= 5, the general
+ *                   kernel 4096 at L 6 .. 12, 8k)                                    stages wx_lat_stages(F), folded, in_stride != n
+ *     2  LATWPD     wx_lattice_wpd_f64 / wx_lattice_wpd_g_f32                        stages
+ *     3  LATF32     wx_lattice_f32                                                   stages, 0, in_stride != n
+ *     4  LATTREE    wx_lattice_tree_f64 / _f32 (wx_lattice_tree_T)                   tree of ones for a full tree, col_stride != 0,
+ *                                                                                    threshold or head on the loads, out_stride != n, in_stride != n
+ *     5  LAT8KT     wx_lattice_tree8k_fwd_f64 / _inv_f64                             depth of the subtree of node (1, 0), of node (1, 1)
+ *     6  LANETREE   wx_lane_tree_f64 / _f32                                          full tree (all-ones mask)
+ *     7  SMALLTREE  wx_dev_small_tree                                                tree status given
+ *     8  HAAR       wx_haar_wpt_f64 / wx_haar_iwpt_f64
+ *     9  TOP        wx_dev_top_levels                                                NL, split mask, deep given, input stride != n, deep mask
+ *    10  TOPWPD     wx_dev_top_levels_wpd
+ *    11  FUSED      k_fwd1d_fused / k_fwd1d_inplace / k_inv1d_fused                  wpd layout, in-place kernel, tree status given,
+ *                                                                                    input 0 dense / 1 strided / 2 colmap, sub-signal (WxSub)
+ *    12  L1TILE     k_level1_tile, K = 1                                             nodes per signal, src_stride != node length, dst_stride != node length,
+ *                                                                                    second source given, second destination given
+ *    13  LEVEL      k_fwd1d_level / k_inv1d_level, K = 1                             tree status given, packet-table stride
+ *    14  GATHER     k_gather_leaves1d, K = 0, always recorded with inverse = 1: iwpd along a tree under mode 1 and getbasiscoef, F = 0
+ *                                                                                    slices k, positions per block
+ *    15  TAIL       wx_dwt_tail, the lane-local deepest levels of a pyramid          tail levels, threshold in thr
+ *    16  ITAIL      wx_idwt_tail                                                     tail levels, threshold in thr
+ *    17  THRFUSED   wx_dev_iwpt1d_thresh: ONE row for the call, followed by the LATTREE or FUSED row of the kernel that took it
+ *                                                                                    th_kind, one threshold per signal, head given, row_lo > 0
+ *    18  THRCOPY    wx_dev_threshold_copy, K = 0                                     th_kind, one threshold per signal, 0, row_lo > 0
+ * _end, _dropped and the WX_EARG cases are those of wx_debug_swt1d_trace_end / _dropped. */
+#define WX_DWT1D_TRACE_FIELDS 16
+#define WX_DWT1D_TRACE_MAX (1 << 16)
+void wx_debug_dwt1d_trace_begin(void);
+int wx_debug_dwt1d_trace_end(int32_t *out, int cap);
+int64_t wx_debug_dwt1d_trace_dropped(void);
 
 /* The schedule of the 1-D redundant inverse (wx_swt_inv_plan, the function wx_swt1d's caller runs) under the current dispatch mode;
  * needs no device.  layout 0 / 1 / 2 = dwt / wpt / wpd container, sm < 0 = average based, haar6 = the caller's wx_haar_swpt6_ok.

@@ -22,6 +22,9 @@
 #include "wx_host.h"
 #include "wx_toptile.h"
 #include "wx_lanetree.h"
+#include "wx_dwt1d_trace.h"
+#include "wx_debug.h"
+#include <vector>
 
 // the tree-driven lattice kernels for either signal type (Float32: dense leaves only, no threshold riding on the loads)
 template <typename T>
@@ -219,6 +222,8 @@ static int launch_level1_tile(const T *src, T *dst, int64_t np, int64_t nper, in
     const int64_t grid = nper * nsig * ((np >> 1) / WX_LT);
     if (grid <= 0 || grid > 0x7fffffff) return wx_set_error(WX_EUNSUPPORTED, "tiled level: grid too large");
     const size_t lds = sizeof(T) * (size_t)(2 * WX_LT + 2 * WX_MAXF + 4);
+    WX_DWT1D_TRACE(WX_R1_L1TILE, INVERSE, sizeof(T), np, wx_dwt1d_trace_take_depth(), 1, nsig, filt.F, (int)nper, src_stride != np, dst_stride != np,
+                   src2 != nullptr, dst2 != nullptr, 256u, (unsigned)grid, lds);
     hipLaunchKernelGGL((k_level1_tile<T, INVERSE>), dim3((unsigned)grid), dim3(256), lds, st, src, dst, (int)np, (int)nper, src_stride,
                        dst_stride, filt, src2, src2_stride, dst2, dst2_stride);
     WX_HIP_CHECK(hipGetLastError());
@@ -1156,6 +1161,8 @@ static int launch_fwd_fused_FNP(const T *x, T *y, int64_t n, int L, int64_t batc
     auto kern = k_fwd1d_fused<T, F, NT, WRITE_ALL, PF>;
     WX_HIP_CHECK(wx_allow_lds(kern, lds));
     const WxFold fold = wx_make_fold(filt);
+    WX_DWT1D_TRACE(WX_R1_FUSED, 0, sizeof(T), n, sub.lvl ? sub.log2 : wx_dwt1d_trace_take_depth(), L, batch, F, WRITE_ALL, 0, status != nullptr,
+                   xs != n, sub.lvl != 0, (unsigned)NT, (unsigned)wx_fused_grid(lds, batch, NT), lds);
     hipLaunchKernelGGL(kern, dim3(wx_fused_grid(lds, batch, NT)), dim3(NT), lds, st, x, y, wx_log2(n), L, batch,
                        xs, ys, filt, fold, status, nstatus, sub.log2, sub.lvl ? sub.lvl : n);
     WX_HIP_CHECK(hipGetLastError());
@@ -1186,6 +1193,8 @@ static int launch_fwd_inplace_FN(const T *x, T *y, int64_t n, int L, int64_t bat
     auto kern = k_fwd1d_inplace<T, F, NT, WRITE_ALL>;
     WX_HIP_CHECK(wx_allow_lds(kern, lds));
     const WxFold fold = wx_make_fold(filt);
+    WX_DWT1D_TRACE(WX_R1_FUSED, 0, sizeof(T), n, wx_dwt1d_trace_take_depth(), L, batch, F, WRITE_ALL, 1, status != nullptr, xs != n, 0, (unsigned)NT,
+                   (unsigned)wx_fused_grid(lds, batch, NT), lds);
     hipLaunchKernelGGL(kern, dim3(wx_fused_grid(lds, batch, NT)), dim3(NT), lds, st, x, y, wx_log2(n), L, batch,
                        xs, ys, filt, fold, status, nstatus);
     WX_HIP_CHECK(hipGetLastError());
@@ -1248,6 +1257,8 @@ static int launch_inv_fused_FNP(const T *xw, T *xh, int64_t n, int L, int64_t ba
     auto kern = k_inv1d_fused<T, F, NT, PF>;
     WX_HIP_CHECK(wx_allow_lds(kern, lds));
     const WxFoldInv fold = wx_make_fold_inv(filt);
+    WX_DWT1D_TRACE(WX_R1_FUSED, 1, sizeof(T), n, wx_dwt1d_trace_take_depth(), L, batch, F, 0, 0, status != nullptr, colmap ? 2 : is != n, 0, (unsigned)NT,
+                   (unsigned)wx_fused_grid(lds, batch, NT), lds);
     hipLaunchKernelGGL(kern, dim3(wx_fused_grid(lds, batch, NT)), dim3(NT), lds, st, xw, xh, wx_log2(n), L, batch,
                        is, os, filt, fold, status, nstatus, colmap, log2blk, thr);
     WX_HIP_CHECK(hipGetLastError());
@@ -1301,13 +1312,16 @@ int wx_dev_iwpt1d_thresh(const T *xw, T *xh, int64_t n, int L, int64_t batch, co
                          int64_t nstatus, const WxThreshArg &thr, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     if constexpr (sizeof(T) == 8) {
         // leaves of a tree (denoiseall(:wpt), Denoising.jl:527): the threshold rides on the loads of the tree-driven lattice inverse
         if (status && !wx_skip_register_kernels()) {
             const int r = wx_lattice_tree_f64(true, (const double *)xw, (double *)xh, n, L, batch, n, 0, filt, status, nstatus, st, &thr);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, 0, thr.t || thr.head, 0, 0);
             if (r) return r < 0 ? r : WX_OK;
         }
     }
+    WX_DWT1D_TRACE_DEPTH(L);
     return launch_inv_fused<T>(xw, xh, n, L, batch, n, n, filt, status, nstatus, nullptr, 0, st, thr);
 }
 template bool wx_iwpt1d_thresh_fusable<double>(int64_t, int, const uint8_t *);
@@ -1326,11 +1340,13 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                  int force_generic)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     const int64_t ys = n * (L + 1);
     if constexpr (sizeof(T) == 8) {
         // 4096-sample signals: rotations in registers, every level leaves through an LDS transposition (wx_lattice.hip)
         if (!force_generic && !wx_skip_register_kernels()) {
             const int r = wx_lattice_wpd_f64((const double *)x, (double *)y, n, L, batch, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F));
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -1338,6 +1354,7 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         // short Float32 signals: the interleaved lattice wpd kernel with Float32 at the two ends (wx_lattice_sgw.hip)
         if (!force_generic && !wx_skip_register_kernels() && n <= 128) {        // 256 samples: the fused LDS kernel is as fast (0.47-0.58 against 0.44-0.50)
             const int r = wx_lattice_wpd_g_f32((const float *)x, (float *)y, n, L, batch, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F));
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -1356,6 +1373,7 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     const int dtop = d0 < L ? d0 : L;
     bool top_done = false;
     if (!force_generic && dtop >= 1 && dtop <= 4 && wx_is_pow2(n) && n >= 8192 && wx_top_levels_ok(filt.F) && x != y) {
+        WX_DWT1D_TRACE(WX_R1_TOPWPD, 0, sizeof(T), n, 0, dtop, batch, filt.F);
         const int rc = wx_dev_top_levels_wpd<T>(x, y, n, dtop, batch, n, ys, n, filt, st);
         if (rc) return rc;
         top_done = true;
@@ -1366,11 +1384,13 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                                       hipMemcpyDeviceToDevice, st));
     for (int d = 0; !top_done && d < dtop; ++d) {
         if (!force_generic && (n >> d) >= 4 * WX_LT && wx_is_pow2(n)) {
+            WX_DWT1D_TRACE_DEPTH(d);
             const int rc = launch_level1_tile<T, false>(y + d * n, y + (d + 1) * n, n >> d, (int64_t)1 << d, batch, ys, ys, filt, st);
             if (rc) return rc;
             continue;
         }
         const int64_t total = batch * (n / 2);
+        WX_DWT1D_TRACE(WX_R1_LEVEL, 0, sizeof(T), n, d, 1, batch, filt.F, 0, 1, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
         hipLaunchKernelGGL(k_fwd1d_level<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, y + d * n,
                            y + (d + 1) * n, ys, ys, (int)n, (int)(n >> d), d, batch, filt,
                            (const uint8_t *)nullptr, (int64_t)0);
@@ -1391,6 +1411,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                  const uint8_t *status, int64_t nstatus, T *scratch, hipStream_t st, int force_generic)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     if (L == 0) {
         WX_HIP_CHECK(hipMemcpyAsync(y, x, sizeof(T) * n * batch, hipMemcpyDeviceToDevice, st));
         return WX_OK;
@@ -1403,17 +1424,20 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
                 const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0);
                 if (r) return r < 0 ? r : WX_OK;
             }
         }
         // very short Float32 signals, full tree (the columns of small images arrive here too): one lane per signal (wx_lanetree.h)
         if (!force_generic && !noreg && !status && n <= 128) {
             const int r = wx_lattice_f32(false, (const float *)x, (float *)y, n, L, batch, n, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), 0, 0);
             if (r) return r < 0 ? r : WX_OK;
         }
         if (!force_generic && !noreg && !status && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && x != y) {
             WxLaneTree lt;
             for (int i = 0; i < 8; ++i) lt.bits[i] = 0xffffffffu;
+            WX_DWT1D_TRACE(WX_R1_LANETREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1);
             return wx_lane_tree_f32(false, (const float *)x, (float *)y, n, L, batch, lt, filt, st);
         }
     }
@@ -1422,11 +1446,13 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         // 0.94 ms of the Walsh-Hadamard kernel at the target's size)
         if (!force_generic && !noreg && !status) {
             const int r = wx_lattice_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF64, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0);
             if (r) return r < 0 ? r : WX_OK;
         }
         // Haar where the lattice does not apply (depths below 6, ...): Walsh-Hadamard formulation (wx_haar.hip)
         if (!force_generic && !noreg && !status) {
             const int r = wx_haar_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_HAAR, 0, sizeof(T), n, 0, L, batch, filt.F);
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -1434,6 +1460,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         // Float32 signals of 4096 samples, full tree: the lattice kernels with Float32 at the two ends (wx_lattice_f32.hip)
         if (!force_generic && !noreg && !status) {
             const int r = wx_lattice_f32(false, (const float *)x, (float *)y, n, L, batch, n, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), 0, 0);
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -1462,6 +1489,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                 T *dst = ((npass - 1 - p) & 1) ? (target == y ? scratch : y) : target;
                 const int NLp = Ltop - 4 * p < 4 ? Ltop - 4 * p : 4;
                 const int64_t np = n >> (4 * p);
+                WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), np, 4 * p, NLp, batch << (4 * p), filt.F, NLp, -1, 0, 0, 0);
                 const int rc = wx_dev_top_levels<T>(false, src, dst, (T *)nullptr, np, NLp, batch << (4 * p), np, np, np, 0xffffffffu, 0u, filt, st);
                 if (rc) return rc;
                 src = dst;
@@ -1473,9 +1501,13 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                     r = wx_lattice_wpt_f64((const double *)scratch, (double *)y, 4096, L - d0, batch << d0, filt, st);
                 else
                     r = wx_lattice_f32(false, (const float *)scratch, (float *)y, 4096, L - d0, batch << d0, 4096, filt, st);
+                if (r == 1)
+                    WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 0, sizeof(T), 4096, d0, L - d0, batch << d0, filt.F, wx_lat_stages(filt.F),
+                                   wx_dwt1d_trace_take_folded(), 0);
                 if (r < 0) return r;
                 if (r == 1) return WX_OK;
             }
+            WX_DWT1D_TRACE_DEPTH(d0);
             return launch_fwd_fused<T, false>(scratch, y, n2, L - d0, batch << d0, n2, n2, filt, nullptr, 0, st);
         }
     }
@@ -1493,6 +1525,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                 T *dst = ((dl - 1 - d) & 1) ? y : scratch;             // depth dl lands in scratch
                 const int64_t nd = n >> d;
                 int rc = WX_OK;
+                WX_DWT1D_TRACE_DEPTH(d);
                 if (wx_fused1d_ok<T>(nd, filt.F))
                     rc = launch_fwd_fused<T, false>(src, dst, nd, 1, batch << d, nd, nd, filt, nullptr, 0, st);
                 else
@@ -1505,8 +1538,12 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                 r = wx_lattice_wpt_f64((const double *)scratch, (double *)y, 4096, L - dl, batch << dl, filt, st);
             else
                 r = wx_lattice_f32(false, (const float *)scratch, (float *)y, 4096, L - dl, batch << dl, 4096, filt, st);
+            if (r == 1)
+                WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 0, sizeof(T), 4096, dl, L - dl, batch << dl, filt.F, wx_lat_stages(filt.F),
+                               wx_dwt1d_trace_take_folded(), 0);
             if (r < 0) return r;
             if (r == 1) return WX_OK;
+            WX_DWT1D_TRACE_DEPTH(dl);
             // not taken after all (alignment): the top levels are in scratch, finish with the fused kernel below
             return launch_fwd_fused<T, false>(scratch, y, 4096, L - dl, batch << dl, 4096, 4096, filt, nullptr, 0, st);
         }
@@ -1516,6 +1553,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         // lines leave after which level (wx_lattice_tree.h; Float32 signals since round 4: wx_lattice_tree32.h)
         if (!force_generic && !noreg && status) {
             const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, status, nstatus, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 0, 0, 0, 0, 0);
             if (r) return r < 0 ? r : WX_OK;
         }
         // a full tree nothing above took, as a tree
@@ -1524,6 +1562,7 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
                 const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0);
                 if (r) return r < 0 ? r : WX_OK;
             }
         }
@@ -1540,13 +1579,20 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     }
     if (d0 > 0) {
         const T *src = x;
+        // in place with an even number of these levels the first one would write the array it reads: it reads a copy instead
+        if (x == y && ((d0 - 1) & 1)) {
+            WX_HIP_CHECK(hipMemcpyAsync(scratch, x, sizeof(T) * n * batch, hipMemcpyDeviceToDevice, st));
+            src = scratch;
+        }
         for (int d = 0; d < d0; ++d) {
             T *dst = ((d0 - 1 - d) & 1) ? y : scratch;                 // depth d0 lands in scratch
             if ((n >> d) >= 4 * WX_LT) {
+                WX_DWT1D_TRACE_DEPTH(d);
                 const int rc = launch_level1_tile<T, false>(src, dst, n >> d, (int64_t)1 << d, batch, n, n, filt, st);
                 if (rc) return rc;
             } else {
                 const int64_t total = batch * (n / 2);
+                WX_DWT1D_TRACE(WX_R1_LEVEL, 0, sizeof(T), n, d, 1, batch, filt.F, 0, 0, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
                 hipLaunchKernelGGL(k_fwd1d_level<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, src, dst, n, n,
                                    (int)n, (int)(n >> d), d, batch, filt, (const uint8_t *)nullptr, (int64_t)0);
             }
@@ -1554,13 +1600,22 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         }
         WX_HIP_CHECK(hipGetLastError());
         const int64_t n2 = n >> d0;
+        WX_DWT1D_TRACE_DEPTH(d0);
         return launch_fwd_fused<T, false>(scratch, y, n2, L - d0, batch << d0, n2, n2, filt, nullptr, 0, st);
     }
     // ping-pong so that the last level lands in y
     const T *src = x;
+    // in place with an odd number of levels the first one would write the array it reads (a thread's inputs are other threads'
+    // outputs): it reads a copy instead
+    if (x == y && !((L - 1) & 1)) {
+        if (!scratch) return wx_set_error(WX_EARG, "wpt in place, one level per launch: an odd number of levels needs the scratch array");
+        WX_HIP_CHECK(hipMemcpyAsync(scratch, x, sizeof(T) * n * batch, hipMemcpyDeviceToDevice, st));
+        src = scratch;
+    }
     for (int d = 0; d < L; ++d) {
         T *dst = ((L - 1 - d) & 1) ? scratch : y;
         const int64_t total = batch * (n / 2);
+        WX_DWT1D_TRACE(WX_R1_LEVEL, 0, sizeof(T), n, d, 1, batch, filt.F, status != nullptr, 0, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
         hipLaunchKernelGGL(k_fwd1d_level<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, src, dst, n, n,
                            (int)n, (int)(n >> d), d, batch, filt, status, nstatus);
         src = dst;
@@ -1608,6 +1663,7 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
                     T *scratch, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     bool lattice;
     const int64_t n2 = wx_dwt_long_plan<T>(n, filt, &lattice);
     if (!n2) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: no plan for this length / filter");
@@ -1627,6 +1683,7 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
             T *deep = scratch + ((pidx & 1) ? n / 2 : 0);
             unsigned split = 0;
             for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);           // heap nodes 1, 2, 4, 8: the approximation branch
+            WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), cur_n, done, NLp, batch, filt.F, NLp, (int)split, 1, cur_n != n, more ? 1 : 0);
             const int rc = wx_dev_top_levels<T>(false, src, y, deep, cur_n, NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
             if (rc) return rc;
             src = deep;
@@ -1639,11 +1696,13 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
                 if (lattice) {
                     const int r = wx_lattice_tree_T<T>(false, src, y, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
                                                       nullptr, n);
+                    if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, Lp - dl, batch, filt.F, 0, 0, 0, n != 4096, n != 4096);
                     if (r < 0) return r;
                     if (r == 1) return WX_OK;
                     if (!wx_fused1d_ok<T>(n2, filt.F)) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: more than 2^31 - 1 signals in one call");
                 }
             }
+            WX_DWT1D_TRACE_DEPTH(dl);
             return launch_fwd_fused<T, false>(src, y, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, st);
         }
         return WX_OK;
@@ -1654,6 +1713,7 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
     int64_t src_stride = n;
     for (int d = 0; d < top; ++d) {
         const int64_t np = n >> d;
+        WX_DWT1D_TRACE_DEPTH(d);
         const int rc = launch_level1_tile<T, false>(src, bufs[d & 1], np, 1, batch, src_stride, S, filt, st, nullptr, 0, y + (np >> 1), n);
         if (rc) return rc;
         src = bufs[d & 1];
@@ -1664,11 +1724,13 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
             if (lattice) {
                 const int r = wx_lattice_tree_T<T>(false, src, y, 4096, Lp - dl, batch, S, 0, filt, status, nstatus, st,
                                                   nullptr, n);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, Lp - dl, batch, filt.F, 0, 0, 0, n != 4096, S != 4096);
                 if (r < 0) return r;
                 if (r == 1) return WX_OK;
                 if (!wx_fused1d_ok<T>(n2, filt.F)) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: more than 2^31 - 1 signals in one call");
             }
         }
+        WX_DWT1D_TRACE_DEPTH(dl);
         return launch_fwd_fused<T, false>(src, y, n2, Lp - dl, batch, S, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, st);
     }
     WX_HIP_CHECK(hipMemcpy2DAsync(y, n * sizeof(T), src, S * sizeof(T), (n >> top) * sizeof(T), batch, hipMemcpyDeviceToDevice, st));
@@ -1680,6 +1742,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
                      const WxThreshArg &thr, T *scratch, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     bool lattice;
     const int64_t n2 = wx_dwt_long_plan<T>(n, filt, &lattice);
     if (!n2) return wx_set_error(WX_EUNSUPPORTED, "idwt of a long signal: no plan for this length / filter");
@@ -1702,6 +1765,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
                 if (lattice) {
                     const int r = wx_lattice_tree_T<T>(true, xw, cur, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
                                                       &thr, n);
+                    if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, Lp, Lp - dl, batch, filt.F, 0, 0, thr.t || thr.head, n != 4096, n != 4096);
                     if (r < 0) return r;
                     done = r == 1;
                     if (!done && !wx_fused1d_ok<T>(n2, filt.F))
@@ -1709,6 +1773,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
                 }
             }
             if (!done) {
+                WX_DWT1D_TRACE_DEPTH(Lp);
                 const int rc = launch_inv_fused<T>(xw, cur, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, nullptr, 0,
                                                    st, thr);
                 if (rc) return rc;
@@ -1720,6 +1785,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
             unsigned split = 0;
             for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);
             T *dst = p == 0 ? y : buf(p - 1);
+            WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n >> (4 * p), 4 * p + NLp, NLp, batch, filt.F, NLp, (int)split, 1, p != 0, more ? 1 : 0);
             const int rc = wx_dev_top_levels<T>(true, xw, dst, buf(p), n >> (4 * p), NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
             if (rc) return rc;
         }
@@ -1735,6 +1801,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
             if (lattice) {
                 const int r = wx_lattice_tree_T<T>(true, xw, cur, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
                                                   &thr, S);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, Lp, Lp - dl, batch, filt.F, 0, 0, thr.t || thr.head, S != 4096, n != 4096);
                 if (r < 0) return r;
                 done = r == 1;
                 if (!done && !wx_fused1d_ok<T>(n2, filt.F))
@@ -1742,6 +1809,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
             }
         }
         if (!done) {
+            WX_DWT1D_TRACE_DEPTH(Lp);
             const int rc = launch_inv_fused<T>(xw, cur, n2, Lp - dl, batch, n, S, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, nullptr, 0,
                                                st, thr);
             if (rc) return rc;
@@ -1752,6 +1820,7 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
     for (int d = top - 1; d >= 0; --d) {
         const int64_t np = n >> d;
         T *dst = d == 0 ? y : bufs[(d - 1) & 1];
+        WX_DWT1D_TRACE_DEPTH(d + 1);
         const int rc = launch_level1_tile<T, true>(bufs[d & 1], dst, np, 1, batch, S, d == 0 ? n : S, filt, st, xw + (np >> 1), n);
         if (rc) return rc;
     }
@@ -1786,6 +1855,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                          T *scratch, bool inverse, hipStream_t st)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     {
         int dl = 0;
         while (((int64_t)4096 << dl) < n) ++dl;
@@ -1829,6 +1899,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                 int dp[2] = {0, 0};
                 for (size_t k = 0; k < sub_nodes.size(); ++k) { ds[sub_nodes[k]] = dsub + k * NS; dp[sub_nodes[k]] = sub_depth[k]; }
                 const int r = wx_lattice_tree8k_inv_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LAT8KT, 1, sizeof(T), n, Lp, Lp, batch, filt.F, dp[0], dp[1]);
                 if (r < 0) return r;
                 if (r == 1) return WX_OK;
             }
@@ -1838,6 +1909,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                 int dp[2] = {0, 0};
                 for (size_t k = 0; k < sub_nodes.size(); ++k) { ds[sub_nodes[k]] = dsub + k * NS; dp[sub_nodes[k]] = sub_depth[k]; }
                 const int r = wx_lattice_tree8k_fwd_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LAT8KT, 0, sizeof(T), n, 0, Lp, batch, filt.F, dp[0], dp[1]);
                 if (r < 0) return r;
                 if (r == 1) return WX_OK;
             }
@@ -1852,6 +1924,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                     if (split(d, j)) smask |= 1u << (((int64_t)1 << d) - 1 + j);
             for (int64_t j : sub_nodes) deepmask |= 1u << j;
             if (!inverse) {
+                WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), n, 0, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
                 const int rc = wx_dev_top_levels<T>(false, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
                 if (rc) return rc;
             }
@@ -1861,9 +1934,12 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                                                             filt, dsub + k * NS, NS, st, nullptr, n)
                                       : wx_lattice_tree_T<T>(false, scratch + off, y + off, 4096, sub_depth[k], batch, n, 0,
                                                             filt, dsub + k * NS, NS, st, nullptr, n);
+                if (r == 1)
+                    WX_DWT1D_TRACE(WX_R1_LATTREE, inverse, sizeof(T), 4096, inverse ? dl + sub_depth[k] : dl, sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
                 if (r < 0) return r;
                 if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal: more than 2^31 - 1 signals in one call");
             }
+            if (inverse) WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n, top, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
             if (inverse) return wx_dev_top_levels<T>(true, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
             return WX_OK;
         }
@@ -1882,6 +1958,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                     if (d < top && split(d, j)) {
                         int64_t j1 = j;
                         while (j1 < cnt && exists(d, j1) && split(d, j1)) ++j1;
+                        WX_DWT1D_TRACE_DEPTH(d);
                         const int rc = launch_level1_tile<T, false>(src + j * np, P(d + 1) + j * np, np, j1 - j, batch, n, n, filt, st);
                         if (rc) return rc;
                         j = j1;
@@ -1896,6 +1973,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                 const int64_t off = sub_nodes[k] * 4096;
                 const int r = wx_lattice_tree_T<T>(false, (dl == 0 ? x : P(dl)) + off, y + off, 4096, sub_depth[k], batch, n,
                                                   0, filt, dsub + k * NS, NS, st, nullptr, n);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
                 if (r < 0) return r;
                 if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal: more than 2^31 - 1 signals in one call");
             }
@@ -1907,6 +1985,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
             const int64_t off = sub_nodes[k] * 4096;
             const int r = wx_lattice_tree_T<T>(true, x + off, Q(dl) + off, 4096, sub_depth[k], batch, n, 0, filt,
                                               dsub + k * NS, NS, st, nullptr, n);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, dl + sub_depth[k], sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
             if (r < 0) return r;
             if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "iwpt of a long signal: more than 2^31 - 1 signals in one call");
         }
@@ -1917,6 +1996,7 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
                 if (d < top && split(d, j)) {
                     int64_t j1 = j;
                     while (j1 < cnt && exists(d, j1) && split(d, j1)) ++j1;
+                    WX_DWT1D_TRACE_DEPTH(d + 1);
                     const int rc = launch_level1_tile<T, true>(Q(d + 1) + j * np, Q(d) + j * np, np, j1 - j, batch, n, n, filt, st);
                     if (rc) return rc;
                     j = j1;
@@ -1944,6 +2024,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
                   T *scratch, T *scratch2, hipStream_t st, int force_generic)
 {
     if (batch == 0 || n == 0) return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(0);
     int64_t is = in_stride;
     if (L == 0) {
         WX_HIP_CHECK(hipMemcpy2DAsync(xh, n * sizeof(T), xw, is * sizeof(T), n * sizeof(T), batch,
@@ -1963,22 +2044,26 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
     if constexpr (sizeof(T) == 4) {
         if (!force_generic && !noreg && !status && !colmap && n <= 128) {
             const int r = wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n);
             if (r) return r < 0 ? r : WX_OK;
         }
         if (!force_generic && !noreg && !status && !colmap && is == n && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && xw != xh) {
             WxLaneTree lt;
             for (int i = 0; i < 8; ++i) lt.bits[i] = 0xffffffffu;
+            WX_DWT1D_TRACE(WX_R1_LANETREE, 1, sizeof(T), n, L, L, batch, filt.F, 1);
             return wx_lane_tree_f32(true, (const float *)xw, (float *)xh, n, L, batch, lt, filt, st);
         }
     }
     if constexpr (sizeof(T) == 8) {
         if (!force_generic && !noreg && !status && !colmap) {
             const int r = wx_lattice_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, is, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF64, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), is != n);
             if (r) return r < 0 ? r : WX_OK;
         }
         // Haar where the lattice does not apply, dense leaves: inverse Walsh-Hadamard formulation (wx_haar.hip)
         if (!force_generic && !noreg && !status && !colmap && is == n) {
             const int r = wx_haar_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_HAAR, 1, sizeof(T), n, L, L, batch, filt.F);
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -1988,11 +2073,13 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
                 const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n);
                 if (r) return r < 0 ? r : WX_OK;
             }
         }
         if (!force_generic && !noreg && !status && !colmap) {
             const int r = wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n);
             if (r) return r < 0 ? r : WX_OK;
         }
     }
@@ -2031,10 +2118,14 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
                         r = wx_lattice_iwpt_f64((const double *)xw, (double *)first, 4096, L - d0, batch << d0, 4096, filt, st);
                     else
                         r = wx_lattice_f32(true, (const float *)xw, (float *)first, 4096, L - d0, batch << d0, 4096, filt, st);
+                    if (r == 1)
+                        WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 1, sizeof(T), 4096, L, L - d0, batch << d0, filt.F,
+                                       wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0);
                     if (r < 0) return r;
                     done = r == 1;
                 }
                 if (!done) {
+                    WX_DWT1D_TRACE_DEPTH(L);
                     const int rc = launch_inv_fused<T>(xw, first, n2, L - d0, batch << d0, n2, n2, filt, nullptr, 0, nullptr, 0, st);
                     if (rc) return rc;
                 }
@@ -2043,6 +2134,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
             for (int p = npass - 1; p >= 0; --p) {
                 const int NLp = Ltop - 4 * p < 4 ? Ltop - 4 * p : 4;
                 const int64_t np = n >> (4 * p);
+                WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), np, 4 * p + NLp, NLp, batch << (4 * p), filt.F, NLp, -1, 0, src == xw && is != n, 0);
                 const int rc = wx_dev_top_levels<T>(true, src, B(p), (T *)nullptr, np, NLp, batch << (4 * p), (src == xw && is != n) ? is : np, np, np,
                                                     0xffffffffu, 0u, filt, st);
                 if (rc) return rc;
@@ -2064,6 +2156,9 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
                 r = wx_lattice_iwpt_f64((const double *)xw, (double *)first, 4096, L - dl, batch << dl, 4096, filt, st);
             else
                 r = wx_lattice_f32(true, (const float *)xw, (float *)first, 4096, L - dl, batch << dl, 4096, filt, st);
+            if (r == 1)
+                WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 1, sizeof(T), 4096, L, L - dl, batch << dl, filt.F, wx_lat_stages(filt.F),
+                               wx_dwt1d_trace_take_folded(), 0);
             if (r < 0) return r;
             if (r == 1) {
                 const T *src2 = first;
@@ -2071,6 +2166,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
                     T *dst = (d & 1) ? scratch : xh;
                     const int64_t nd = n >> d;
                     int rc = WX_OK;
+                    WX_DWT1D_TRACE_DEPTH(d + 1);
                     if (wx_fused1d_ok<T>(nd, filt.F))
                         rc = launch_inv_fused<T>(src2, dst, nd, 1, batch << d, nd, nd, filt, nullptr, 0, nullptr, 0, st);
                     else
@@ -2088,6 +2184,7 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
         if (!force_generic && !noreg && status) {
             const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, colmap ? n : 0, filt, status,
                                               nstatus, st);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, colmap != nullptr, 0, 0, is != n);
             if (r) return r < 0 ? r : WX_OK;
         }
         if (!force_generic && !noreg && !status && !colmap && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 &&
@@ -2095,12 +2192,15 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
             const uint8_t *ones = wx_full_tree_ones(st);
             if (ones) {
                 const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st);
+                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n);
                 if (r) return r < 0 ? r : WX_OK;
             }
         }
     }
-    if (!force_generic && wx_fused1d_ok<T>(n, filt.F))
+    if (!force_generic && wx_fused1d_ok<T>(n, filt.F)) {
+        WX_DWT1D_TRACE_DEPTH(L);
         return launch_inv_fused<T>(xw, xh, n, L, batch, is, n, filt, status, nstatus, colmap, log2blk, st);
+    }
     // long signals, full tree, dense leaves: depths L-1 .. d0 on chip as (n >> d0, batch << d0) sub-signals,
     // the remaining d0 levels one per launch (mirror of wx_dev_wpt1d)
     int d0 = 0;
@@ -2117,16 +2217,19 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
     if (d0 > 0) {
         T *fbuf = (d0 & 1) ? scratch : xh;                              // as if depth d0 were one more generic level
         const int64_t n2 = n >> d0;
+        WX_DWT1D_TRACE_DEPTH(L);
         int rc = launch_inv_fused<T>(xw, fbuf, n2, L - d0, batch << d0, n2, n2, filt, nullptr, 0, nullptr, 0, st);
         if (rc) return rc;
         const T *src2 = fbuf;
         for (int d = d0 - 1; d >= 0; --d) {
             T *dst = (d & 1) ? scratch : xh;
             if ((n >> d) >= 4 * WX_LT) {
+                WX_DWT1D_TRACE_DEPTH(d + 1);
                 const int rc = launch_level1_tile<T, true>(src2, dst, n >> d, (int64_t)1 << d, batch, n, n, filt, st);
                 if (rc) return rc;
             } else {
                 const int64_t total = batch * (n / 2);
+                WX_DWT1D_TRACE(WX_R1_LEVEL, 1, sizeof(T), n, d + 1, 1, batch, filt.F, 0, 0, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
                 hipLaunchKernelGGL(k_inv1d_level<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, src2, dst, n, n, (int)n,
                                    (int)(n >> d), d, batch, filt, (const uint8_t *)nullptr, (int64_t)0);
             }
@@ -2137,8 +2240,15 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
     }
     const T *src = xw;
     int64_t src_stride = is;
+    // in place with an odd number of levels the first one would write the array it reads: it reads a copy instead
+    if (!colmap && xw == xh && !((L - 1) & 1)) {                 // (xw == xh: dense leaves, is == n)
+        if (!scratch) return wx_set_error(WX_EARG, "iwpt in place, one level per launch: an odd number of levels needs the scratch array");
+        WX_HIP_CHECK(hipMemcpyAsync(scratch, xw, sizeof(T) * n * batch, hipMemcpyDeviceToDevice, st));
+        src = scratch;
+    }
     if (colmap) {
         const int64_t total = batch * n;
+        WX_DWT1D_TRACE(WX_R1_GATHER, 1, sizeof(T), n, L, 0, batch, 0, (int)(is / n), 1 << log2blk, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
         hipLaunchKernelGGL(k_gather_leaves1d<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, xw, scratch2,
                            (int)n, (int)(is / n), batch, colmap, 1 << log2blk);
         src = scratch2;
@@ -2147,6 +2257,8 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
     for (int d = L - 1; d >= 0; --d) {
         T *dst = (d & 1) ? scratch : xh;
         const int64_t total = batch * (n / 2);
+        WX_DWT1D_TRACE(WX_R1_LEVEL, 1, sizeof(T), n, d + 1, 1, batch, filt.F, status != nullptr, src_stride != n, 0, 0, 0, 256u,
+                       (unsigned)wx_grid_for(total, 256), 0);
         hipLaunchKernelGGL(k_inv1d_level<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, src, dst, src_stride,
                            n, (int)n, (int)(n >> d), d, batch, filt, status, nstatus);
         src = dst;
@@ -2162,6 +2274,7 @@ int wx_dev_getbasiscoef1d(const T *Xw, T *out, int64_t n, int k, int64_t batch, 
 {
     if (batch == 0 || n == 0) return WX_OK;
     const int64_t total = batch * n;
+    WX_DWT1D_TRACE(WX_R1_GATHER, 1, sizeof(T), n, 0, 0, batch, 0, k, blk, 0, 0, 0, 256u, (unsigned)wx_grid_for(total, 256), 0);
     hipLaunchKernelGGL(k_gather_leaves1d<T>, dim3(wx_grid_for(total, 256)), dim3(256), 0, st, Xw, out, (int)n, k,
                        batch, colmap, blk);
     WX_HIP_CHECK(hipGetLastError());
@@ -2177,6 +2290,60 @@ int wx_dev_getbasiscoef1d(const T *Xw, T *out, int64_t n, int k, int64_t batch, 
     template int wx_dev_getbasiscoef1d<T>(const T *, T *, int64_t, int, int64_t, const int *, int, hipStream_t);
 WX_INST(double)
 WX_INST(float)
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// launch record of the parity suite (wx_debug.h; rows appended by WX_DWT1D_TRACE, wx_dwt1d_trace.h)
+// ---------------------------------------------------------------------------------------------------------------------------------
+std::atomic<int> wx_dwt1d_trace_armed{0};
+static std::mutex g_dwt1d_trace_mu;                      // test_gpu_stress.py calls the library from several threads
+static std::vector<int32_t> g_dwt1d_trace_rows;
+static int64_t g_dwt1d_trace_dropped = 0;
+static thread_local int g_dwt1d_trace_depth = 0, g_dwt1d_trace_folded = 0;
+
+void wx_dwt1d_trace_set_depth(int depth) { g_dwt1d_trace_depth = depth; }
+void wx_dwt1d_trace_set_folded(int folded) { g_dwt1d_trace_folded = folded; }
+int wx_dwt1d_trace_take_depth() { const int d = g_dwt1d_trace_depth; g_dwt1d_trace_depth = 0; return d; }
+int wx_dwt1d_trace_take_folded() { const int f = g_dwt1d_trace_folded; g_dwt1d_trace_folded = 0; return f; }
+
+void wx_dwt1d_trace_add(int route, int inverse, size_t esz, int64_t n, int depth, int K, int64_t signals, int F, int e0, int e1, int e2, int e3,
+                        int e4, unsigned block, unsigned grid, size_t lds)
+{
+    std::lock_guard<std::mutex> lk(g_dwt1d_trace_mu);
+    if (!wx_dwt1d_trace_armed.load(std::memory_order_relaxed)) return;
+    if (g_dwt1d_trace_rows.size() >= (size_t)WX_DWT1D_TRACE_MAX * WX_DWT1D_TRACE_FIELDS) { ++g_dwt1d_trace_dropped; return; }
+    const int64_t big = 0x7fffffff;
+    const int32_t row[WX_DWT1D_TRACE_FIELDS] = {route, inverse ? 1 : 0, (int32_t)esz, (int32_t)(n > big ? big : n), depth, K,
+                                                (int32_t)(signals > big ? big : signals), F, e0, e1, e2, e3, e4, (int32_t)block,
+                                                (int32_t)(grid > big ? big : grid), (int32_t)lds};
+    g_dwt1d_trace_rows.insert(g_dwt1d_trace_rows.end(), row, row + WX_DWT1D_TRACE_FIELDS);
+}
+
+extern "C" void wx_debug_dwt1d_trace_begin(void)
+{
+    std::lock_guard<std::mutex> lk(g_dwt1d_trace_mu);
+    g_dwt1d_trace_rows.clear();
+    g_dwt1d_trace_dropped = 0;
+    wx_dwt1d_trace_armed.store(1);
+}
+
+extern "C" int wx_debug_dwt1d_trace_end(int32_t *out, int cap)
+{
+    std::lock_guard<std::mutex> lk(g_dwt1d_trace_mu);
+    if (!out || cap <= 0) return wx_set_error(WX_EARG, "wx_debug_dwt1d_trace_end: no room for a single entry");
+    if (!wx_dwt1d_trace_armed.load()) return wx_set_error(WX_EARG, "wx_debug_dwt1d_trace_end without wx_debug_dwt1d_trace_begin");
+    wx_dwt1d_trace_armed.store(0);
+    const size_t rows = g_dwt1d_trace_rows.size() / WX_DWT1D_TRACE_FIELDS;
+    const size_t ncopy = rows < (size_t)cap ? rows : (size_t)cap;
+    for (size_t i = 0; i < ncopy * WX_DWT1D_TRACE_FIELDS; ++i) out[i] = g_dwt1d_trace_rows[i];
+    std::vector<int32_t>().swap(g_dwt1d_trace_rows);
+    return (int)rows;
+}
+
+extern "C" int64_t wx_debug_dwt1d_trace_dropped(void)
+{
+    std::lock_guard<std::mutex> lk(g_dwt1d_trace_mu);
+    return g_dwt1d_trace_dropped;
+}
 
 #ifdef WX_STAMPS
 extern "C" int wx_debug_read_stamps(unsigned long long *out, int reset)

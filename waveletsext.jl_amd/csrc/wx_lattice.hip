@@ -2,6 +2,7 @@
 // 4096-sample signals; the interleaved shorter signals are launched from wx_lattice_sh.hip (a separate translation unit so
 // that the two sets of kernel instantiations compile in parallel)
 #include "wx_lattice_fold.h"
+#include "wx_dwt1d_trace.h"
 
 // Lattice factorisation of the polyphase matrix (long double): G(w) = [[Qe, Qo], [-w^J Qo(1/w), w^J Qe(1/w)]]
 // = R_J Lambda(w) R_{J-1} ... Lambda(w) R_0 with R_j = c_j [[1, t_j], [-t_j, 1]], Lambda = diag(1, w).
@@ -265,6 +266,7 @@ static int wx_lattice_launch(bool inverse, const double *x, double *y, int64_t n
             }
             const hipError_t ef = hipGetLastError();
             if (ef != hipSuccess) return wx_set_hip_error(ef, "lattice iwpt launch (folded)", __FILE__, __LINE__);
+            WX_DWT1D_TRACE_FOLDED(1);                  // the caller's LATF64 row: these arguments do not tell this kernel from the general one
             return 1;
         }
     }
@@ -282,6 +284,7 @@ static int wx_lattice_launch(bool inverse, const double *x, double *y, int64_t n
 #undef WX_GO
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice wpt launch", __FILE__, __LINE__);
+    WX_DWT1D_TRACE_FOLDED(0);
     return 1;
 }
 
@@ -335,12 +338,14 @@ int wx_lattice_iwpt8k_f64(const double *xw, double *y, int L, int64_t batch, int
 
 int wx_lattice_wpt_f64(const double *x, double *y, int64_t n, int L, int64_t batch, const WxFilt &filt, hipStream_t st)
 {
+    WX_DWT1D_TRACE_FOLDED(0);                      // (only wx_lattice_launch's folded inverse sets it)
     if (n == 8192) return wx_lattice_wpt8k_f64(x, y, L, batch, filt, st);
     return wx_lattice_launch(false, x, y, n, L, batch, n, filt, st);
 }
 int wx_lattice_iwpt_f64(const double *xw, double *y, int64_t n, int L, int64_t batch, int64_t in_stride, const WxFilt &filt,
                         hipStream_t st)
 {
+    WX_DWT1D_TRACE_FOLDED(0);                      // a note no caller took does not reach this call's row
     if (n == 8192) return wx_lattice_iwpt8k_f64(xw, y, L, batch, in_stride, filt, st);
     return wx_lattice_launch(true, xw, y, n, L, batch, in_stride, filt, st);
 }
