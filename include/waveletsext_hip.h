@@ -408,6 +408,24 @@ int wx_treeselect_batch_f64(double *costs, int64_t ncost, int64_t m, int64_t n, 
 int wx_treeselect_batch_f32(float *costs, int64_t ncost, int64_t m, int64_t n, int type_max, int64_t batch,
                             uint8_t *trees, void *stream);
 
+/* Per-signal best bases straight from the signals: bestbasistreeall(wpdall(x, wt, L), BB(cost)) (BestBasis.jl:59-83, 253-262 over
+ * tree_costs, bestbasis/bestbasis_tree.jl:210-233) without the (n, L+1, batch) packet table.  x (n, batch) -> trees (n - 1, batch), one
+ * byte per node in the layout of wx_treeselect_batch_*; costs is NULL or receives the (2^(L+1) - 1, batch) costs as tree_costs returns
+ * them (not the ones the selection has folded).  cost_kind as wx_bb_costs_*.  Pointers may be host or device; device calls are
+ * asynchronous on `stream`.  Before a device is needed: n not dyadic or L outside 0 ... maxtransformlevels(n) -> WX_EASSERT; NULL x /
+ * qmf / trees or another cost_kind -> WX_EARG; batch == 0 -> WX_OK with nothing written.
+ * One kernel holds a signal's levels, costs and selection flags in LDS (dyadic n >= 8, even filters of 2 ... 20 taps, 160 KiB: Float64
+ * up to n = 4096 at full depth, Float32 up to 8192); every other shape runs chunks of signals through wx_wpd1d_*, wx_bb_costs_* and
+ * wx_treeselect_batch_* with the chunk's table in scratch of at most 256 MiB (or one signal's table).  The same input gives the same
+ * bytes on every call.
+ * wx_wpd_bb_last_route: the way the last of these calls went on the calling thread: 0 = none yet, or that call returned an error;
+ * 1 = the fused kernel; 2 = chunks through the table kernels; 3 = nothing to transform (L = 0 or batch = 0). */
+int wx_wpd_bbtrees_f64(const double *x, int64_t n, int64_t L, int64_t batch, const double *qmf, int F, int cost_kind, uint8_t *trees,
+                       double *costs, void *stream);
+int wx_wpd_bbtrees_f32(const float *x, int64_t n, int64_t L, int64_t batch, const double *qmf, int F, int cost_kind, uint8_t *trees,
+                       float *costs, void *stream);
+int wx_wpd_bb_last_route(void);
+
 /* ------------------------------------------------------------------------------------------
  * Denoising core -- SURVEY 8(f) row 1: the two device steps between a forward and an inverse batch transform
  * (denoise / denoiseall, Denoising.jl:483-712).  X (n, k, batch) is any coefficient container of this header:

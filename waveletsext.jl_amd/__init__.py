@@ -24,7 +24,8 @@ from .acwt import (acdwt, acdwt_, acdwtall, iacdwt, iacdwt_, iacdwtall, acwpt, a
 from .bestbasis import (JBB, LoglpCost, NormCost, tree_costs, bestbasistree, bestbasis_treeselection,   # noqa: F401
                         jbb_moments, costs_from_moments, acwpd_jbb_moments,
                         BB, ShannonEntropyCost, LogEnergyEntropyCost, bestbasistreeall,
-                        LSDB, DifferentialEntropyCost, lsdb_entropy)
+                        LSDB, DifferentialEntropyCost, lsdb_entropy,
+                        wpd_bestbasistreeall, bestbasiscoefall, wpd_bb_route)
 from .denoising import (HardTH, SoftTH, SemiSoftTH, SteinTH, VisuShrink, SureShrink, RelErrorShrink,   # noqa: F401,E402
                         noisest, noisestall, threshold, denoise, denoiseall, surethreshold, relerrorthreshold,
                         surethresholdall, relerrorthresholdall)

@@ -212,6 +212,9 @@ _PLAIN_SIGS = {
     "wx_lsdb_costs2d_f32": [_P, _L, _L, _L, _L, _I, _P, _P],
     "wx_treeselect_batch_f64": [_P, _L, _L, _L, _I, _L, _P, _P],
     "wx_treeselect_batch_f32": [_P, _L, _L, _L, _I, _L, _P, _P],
+    "wx_wpd_bbtrees_f64": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
+    "wx_wpd_bbtrees_f32": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
+    "wx_wpd_bb_last_route": [],
     "wx_wavemult_plan_info": [_P, _P],
     "wx_wavemult_plan_destroy": [_P],
     "wx_comm_unique_id": [_P],
@@ -324,6 +327,22 @@ def wpt_trees_route():
     """which way the last wptall / iwptall / iwpdall / getbasiscoefall / denoiseall / iswpdall / iacwpdall call with one tree per signal went on this thread
     (wx_wpt_trees_last_route): one of WPT_TREES_ROUTES' strings; "none" before the first such call and after one that raised"""
     return WPT_TREES_ROUTES[lib().wx_wpt_trees_last_route()]
+
+
+def wpd_bb_route():
+    """which way the last wpd_bestbasistreeall / bestbasiscoefall call went on this thread (wx_wpd_bb_last_route,
+    include/waveletsext_hip.h): 0 = none yet, or that call raised; 1 = the fused kernel; 2 = chunks of signals through the table
+    kernels; 3 = nothing to transform (L = 0, no signals)"""
+    return int(lib().wx_wpd_bb_last_route())
+
+
+def wpd_bb_grid(n, L, F, elem_size, batch):
+    """csrc/wx_debug.h: the workgroups the fused kernel of wx_wpd_bbtrees_* is launched with for this shape, by the function the
+    launch calls; 0 outside the kernel's window.  Needs no device."""
+    f = lib().wx_debug_wpd_bb_grid
+    f.argtypes = [_L, _I, _I, _I, _L]
+    f.restype = _I
+    return int(f(int(n), int(L), int(F), int(elem_size), int(batch)))
 
 
 # csrc/wx_debug.h: route ids of the 1-D redundant transforms' launch record

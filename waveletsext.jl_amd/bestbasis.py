@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._lib import wpd_bb_route  # noqa: F401
 from ._arrays import Arg, is_torch, qmf_arg, to_numpy
 from .dwt import _call
 from .filters import ArgumentError
@@ -296,3 +297,53 @@ def acwpd_jbb_moments(x, wt, L=None, accumulate_into=None):
     qq, qp, F = qmf_arg(wt)
     _call("wx_acwpd_jbb_moments", x.suffix, x.ptr, s.ptr, q.ptr, n, L, N, qp, F, acc, x.stream())
     return s.arr, q.arr
+
+
+def wpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=False):
+    """bestbasistreeall(wpdall(x, wt, L), BB(cost)) (BestBasis.jl:253-262, bestbasis_tree.jl:210-233) straight from the signals
+    x (n, N): the (n, L+1, N) packet table is never written.  Returns what bestbasistreeall returns, a column-major boolean
+    (n-1, N) matrix, or with device=True (x a device tensor) the torch.bool view that wptall / iwptall / denoiseall take as it
+    is; return_costs=True adds the (2^(L+1)-1, N) costs, as tree_costs gives them for every signal."""
+    method = BB() if method is None else method
+    if not isinstance(method, BB):
+        raise TypeError("wpd_bestbasistreeall takes a BB method (BestBasis.jl:253)")
+    if method.redundant:
+        raise TypeError("wpd_bestbasistreeall: redundant tables keep their table, use bestbasistreeall(swpdall(...), BB(redundant=True))")
+    if device and not (is_torch(x) and x.device.type != "cpu"):
+        raise TypeError("wpd_bestbasistreeall(..., device=True) takes a device tensor")
+    xa = Arg(x)
+    assert xa.arr.ndim == 2
+    n, N = xa.shape
+    Lmax = maxtransformlevels(n)
+    L = Lmax if L is None else int(L)
+    kind = 0 if isinstance(method.cost, ShannonEntropyCost) else 1
+    ntree, ncost = max(n - 1, 0), (1 << (max(L, 0) + 1)) - 1
+    costs = xa.new((ncost, N)) if return_costs else None
+    if xa.kind == "torch":
+        import torch
+        trees = torch.empty((N, ntree), dtype=torch.uint8, device=xa.device)
+        tp = ctypes.c_void_p(trees.data_ptr())
+    else:
+        trees = np.empty((N, ntree), dtype=np.uint8)
+        tp = ctypes.c_void_p(trees.ctypes.data)
+    q, qp, F = qmf_arg(wt)
+    _call("wx_wpd_bbtrees", xa.suffix, xa.ptr, n, L, N, qp, F, kind, tp, costs.ptr if return_costs else ctypes.c_void_p(0),
+          xa.stream())
+    if device:
+        t = trees.T.view(torch.bool)                   # (n-1, N) column-major; the kernel writes bytes of 0 / 1
+    elif xa.kind == "torch":
+        host = torch.empty(trees.shape, dtype=torch.uint8, pin_memory=True)
+        host.copy_(trees, non_blocking=True)
+        torch.cuda.current_stream(trees.device).synchronize()
+        t = host.numpy().T.view(np.bool_)
+    else:
+        t = trees.T.view(np.bool_)
+    return (t, costs.arr) if return_costs else t
+
+
+def bestbasiscoefall(x, wt, L=None, method=None, device=False):
+    """(wptall(x, wt, trees), trees) with trees = wpd_bestbasistreeall(x, wt, L, method, device): every signal's coefficients in its own
+    best basis and the bases, without the packet table on either side"""
+    from .dwt import wptall
+    trees = wpd_bestbasistreeall(x, wt, L, method, device=device)
+    return wptall(x, wt, trees), trees

@@ -10,6 +10,7 @@
 #include "wx_host.h"
 #include "wx_kernels.h"
 #include "wx_bbcost.h"
+#include "wx_bb_select.h"
 
 #define WX_REQUIRE(cond, code, msg) \
     do { if (!(cond)) return wx_set_error(code, msg); } while (0)
@@ -309,10 +310,7 @@ __global__ __launch_bounds__(256) void k_bb_costs2d(const T *__restrict__ X, con
     }
 }
 
-// Bottom-up selection, one workgroup per signal.  The sequential reference (i = ntree..1: keep the
-// children's sum when it beats the parent, else delete_subtree!(i)) is level-synchronous: a node's
-// decision needs only its children's final costs, and deleting a subtree clears exactly the nodes that
-// have a pruned ancestor-or-self, so   tree[i] = full[i] && !pruned[i] && tree[parent(i)].
+// Bottom-up selection, one workgroup per signal: the two level-synchronous sweeps of wx_bb_select.h.
 // costs (T, mutated like the reference) and the flags live in LDS.
 // GM: cost vectors that do not fit a CU's LDS (signals of more than about 8000 samples' worth of nodes) are updated where they are, in
 // global memory, with the flags in a scratch row (the reference has no limit: BestBasis.jl:253-262)
@@ -338,36 +336,9 @@ __global__ __launch_bounds__(256) void k_bb_treeselect(T *__restrict__ costs, in
         for (; i < ncost; i += 256) c[i] = gc[i];
     }
     __syncthreads();
-    // first 1-based index of depth d: binary 2^d, quad (4^d - 1)/3 + 1
-    auto first = [](int d) -> int64_t { return ARITY == 2 ? ((int64_t)1 << d) : ((((int64_t)1 << (2 * d)) - 1) / 3 + 1); };
-    for (int d = L - 1; d >= 0; --d) {
-        const int64_t lo = first(d), hi = first(d + 1);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-            const T pc = c[i - 1];
-            T cc;
-            if (ARITY == 2) cc = (T)(c[2 * i - 1] + c[2 * i]);
-            else cc = (T)((T)((T)(c[4 * i - 3] + c[4 * i - 2]) + c[4 * i - 1]) + c[4 * i]);
-            const bool better = type_max ? (cc > pc) : (cc < pc);
-            if (better) c[i - 1] = cc;
-            flag[i - 1] = better ? 0 : 1;
-        }
-        __syncthreads();
-    }
-    // top down, in place: flag[] of shallower depths already holds the tree bit
-    for (int d = 0; d < L; ++d) {
-        const int64_t lo = first(d), hi = first(d + 1);
-        for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-            bool keep = !flag[i - 1];
-            if (i > 1) {
-                const int64_t par = ARITY == 2 ? (i >> 1) : ((i + 2) >> 2);
-                keep = keep && flag[par - 1];
-            }
-            flag[i - 1] = keep ? 1 : 0;
-        }
-        __syncthreads();
-    }
+    bb_select_sweeps<T, ARITY>(c, flag, L, type_max, (unsigned)threadIdx.x, (unsigned)blockDim.x, [] { __syncthreads(); });
     uint8_t *out = trees + sig * ntree;
-    const int64_t nfull = first(L) - 1;
+    const int64_t nfull = ARITY == 2 ? (((int64_t)1 << L) - 1) : ((((int64_t)1 << (2 * L)) - 1) / 3);
     for (int64_t i = threadIdx.x; i < ntree; i += blockDim.x) out[i] = i < nfull ? flag[i] : 0;
     if (!GM)
         for (int64_t i = threadIdx.x; i < ncost; i += blockDim.x) gc[i] = c[i];
@@ -395,26 +366,7 @@ __global__ __launch_bounds__(256) void k_bb_treeselect_w(T *__restrict__ costs, 
     };
     for (int64_t i = lane; i < ncost; i += 64) c[i] = gc[i];
     wsync();
-    for (int d = L - 1; d >= 0; --d) {
-        const int64_t lo = (int64_t)1 << d, hi = (int64_t)2 << d;
-        for (int64_t i = lo + lane; i < hi; i += 64) {
-            const T pc = c[i - 1];
-            const T cc = (T)(c[2 * i - 1] + c[2 * i]);
-            const bool better = type_max ? (cc > pc) : (cc < pc);
-            if (better) c[i - 1] = cc;
-            flag[i - 1] = better ? 0 : 1;
-        }
-        wsync();
-    }
-    for (int d = 0; d < L; ++d) {
-        const int64_t lo = (int64_t)1 << d, hi = (int64_t)2 << d;
-        for (int64_t i = lo + lane; i < hi; i += 64) {
-            bool keep = !flag[i - 1];
-            if (i > 1) keep = keep && flag[(i >> 1) - 1];
-            flag[i - 1] = keep ? 1 : 0;
-        }
-        wsync();
-    }
+    bb_select_sweeps<T, 2>(c, flag, L, type_max, lane, 64, wsync);
     uint8_t *out = trees + sig * ntree;
     const int64_t nfull = ((int64_t)1 << L) - 1;
     for (int64_t i = lane; i < ntree; i += 64) out[i] = i < nfull ? flag[i] : 0;

@@ -171,6 +171,11 @@ int wx_debug_pack_tree1d(const uint8_t *tree, int64_t n, uint32_t *words);
  * class and chunk, chunks of at least 64 signals of the average class, classes x chunks <= 65535.  Needs no device.  Returns
  * WX_EARG (-2) for arguments those entry points refuse: nk < 1, N outside 1 .. 2^31 - 1, nc outside 2 .. 65535. */
 int wx_debug_ldb_chunks(int64_t nk, int64_t N, int nc);
+
+/* The workgroups wx_wpd_bbtrees_* launches its fused kernel with (wx_wpd_bb.hip) for `batch` signals of n samples at depth L under a
+ * filter of F taps, elem_size 8 / 4 = Float64 / Float32, by the very functions the launch calls; 0 when the shape is outside the
+ * kernel's window (the chunked route) or L < 1.  Needs no device. */
+int wx_debug_wpd_bb_grid(int64_t n, int L, int F, int elem_size, int64_t batch);
 #ifdef __cplusplus
 }
 #endif

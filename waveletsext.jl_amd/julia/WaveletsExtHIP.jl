@@ -765,6 +765,21 @@ function bestbasistreeall(X::HIP{T}, method::BB; device::Bool = false) where T<:
     check(wx_treeselect_batch(T, costs, ncost, sig[1], length(sig) == 2 ? sig[2] : 0, 0, N, trees, stream()))
     return BitMatrix(trees .!= 0)
 end
+# wpdall + bestbasistreeall(BB) fused: what `bestbasistreeall(wpdall(x, wt, L), BB(cost))` returns, straight from the signals -- the
+# (n, L+1, N) table is never written (wx_wpd_bbtrees_*: one kernel with a signal's levels, costs and flags in LDS; chunks of signals
+# through the table kernels outside its window).  device = true as bestbasistreeall; costs = true adds the (2^(L+1)-1, N) costs.
+function wpd_bestbasistreeall(x::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(size(x, 1)), method::BB = BB();
+                              device::Bool = false, costs::Bool = false) where T<:FT
+    method.redundant && throw(ArgumentError("redundant tables keep their table: bestbasistreeall(swpdall(x, wt, L), method)"))
+    n, N = size(x); q = qmfvec(wt)
+    trees = device ? newlike(x, UInt8, (max(n - 1, 0), N)) : Matrix{UInt8}(undef, max(n - 1, 0), N)
+    c = !costs ? C_NULL : (device ? newlike(x, T, ((1 << (L + 1)) - 1, N)) : Matrix{T}(undef, (1 << (L + 1)) - 1, N))
+    check(wx_wpd_bbtrees(T, raw(x), n, L, N, q, length(q), bbkind(method.cost), trees, c, stream()))
+    t = device ? HIP(trees) : BitMatrix(trees .!= 0)
+    return costs ? (t, c) : t
+end
+"the way the last wpd_bestbasistreeall call went on this thread (wx_wpd_bb_last_route, include/waveletsext_hip.h)"
+wpd_bb_route() = (:none, :fused, :chunked, :trivial)[Int(wx_wpd_bb_last_route()) + 1]
 
 # acwpdall + JBB fused (BASELINE config 5): what `bestbasistree(acwpdall(x, wt, L), JBB(redundant = true))` returns,
 # without the (n, 2^(L+1)-1, N) table -- 16 TiB for 262144 signals of 2048 samples.  The library walks the batch in
