@@ -51,13 +51,10 @@ Routes (csrc/wx_debug.h) and the cases that pin them:
   THRFUSED   pyr-*-1024 inverse (head, no threshold), thr-*-1024-tree, thr-f64-1024-hard, thr-f64-1024-tail, thr-f64-128-pyr
   THRCOPY    thr-f64-64-short (then LATTREE), thr-f64-1024-full (then LATF64), thr-f64-16384-pyr (then the long pyramid)
 
-Not reachable from the 1-D entry points (the condition is quoted from the code; nothing is deleted here):
-  * the second long-signal block of wx_dev_wpt1d / wx_dev_iwpt1d (`dl >= 1 && dl <= 4 && n == ((int64_t)4096 << dl) && L - dl >= 6 &&
-    x != y && wx_lattice_applicable_f64(filt)`): it sits behind `!force_generic && !status && x != y && wx_is_pow2(n) && n > 4096 &&
-    wx_top_levels_ok(filt.F)`, whose lat branch takes the same shapes; wx_top_levels_ok is `F >= 2 && F <= 20 && (F & 1) == 0` and
-    wx_lattice_applicable_f64 wants `filt.F / 2 <= WX_LAT_MAXS` (20 taps), so the first block never leaves it a filter.
-  * the L1TILE branch of wx_dev_dwt_long / wx_dev_idwt_long (scratch pitch `S = n / 2 + n / 4`): wx_dwt_long_plan returns non-zero
-    only with `wx_top_levels_ok(filt.F)` or `wx_fused1d_ok<T>(n2, filt.F)`, and the latter's switch ends at 20 taps as well.
+Not reachable from the 1-D entry points (the condition is quoted from the code).  Four branches that stood in this list or beside it
+have since been deleted, with their proofs in profiles/dwt1d_routes.md, "Removed as unreachable": the second long-signal block of
+wx_dev_wpt1d / wx_dev_iwpt1d, the L1TILE branch of wx_dev_dwt_long / wx_dev_idwt_long, the split form of k_level1_tile that only
+that branch used, and the per-level fallback of wx_dev_wpt_long_tree.  What is left:
   * the `d0 > 0` blocks of wx_dev_wpt1d / wx_dev_iwpt1d out of place: they need `!wx_fused1d_ok<T>(n, filt.F)` with a filter of
     at most 20 taps, i.e. n > 8192 (Float32 16384), where the first long-signal block applies.  In place (`x is y`) they are
     reached: ip-f64-16384-L3.

@@ -139,7 +139,7 @@ int64_t wx_debug_dwt2d_trace_dropped(void);
  *    11  FUSED      k_fwd1d_fused / k_fwd1d_inplace / k_inv1d_fused                  wpd layout, in-place kernel, tree status given,
  *                                                                                    input 0 dense / 1 strided / 2 colmap, sub-signal (WxSub)
  *    12  L1TILE     k_level1_tile, K = 1                                             nodes per signal, src_stride != node length, dst_stride != node length,
- *                                                                                    second source given, second destination given
+ *                                                                                    0, 0 (unused; the pinned rows keep their layout)
  *    13  LEVEL      k_fwd1d_level / k_inv1d_level, K = 1                             tree status given, packet-table stride
  *    14  GATHER     k_gather_leaves1d, K = 0, always recorded with inverse = 1: iwpd along a tree under mode 1 and getbasiscoef, F = 0
  *                                                                                    slices k, positions per block

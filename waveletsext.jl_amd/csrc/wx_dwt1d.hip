@@ -45,6 +45,23 @@ template <typename T> static bool wx_lattice_tree_applicable_T(int64_t n, const 
     if constexpr (sizeof(T) == 8) return wx_lattice_tree_applicable_f64(n, filt);
     else return wx_lattice_tree_applicable_f32(n, filt);
 }
+// the full-tree lattice kernels for either signal type, dense signals (wx_lattice.hip, wx_lattice_f32.hip)
+template <typename T> static int wx_lattice_full_T(bool inverse, const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt &filt, hipStream_t st)
+{
+    if constexpr (sizeof(T) == 4) return wx_lattice_f32(inverse, (const float *)x, (float *)y, n, L, batch, n, filt, st);
+    else if (inverse) return wx_lattice_iwpt_f64((const double *)x, (double *)y, n, L, batch, n, filt, st);
+    else return wx_lattice_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st);
+}
+
+// One attempt of the dispatch, as one statement: `call` is a launcher that answers 0 = declined, 1 = launched, < 0 = error, `row` the
+// WX_DWT1D_TRACE hook of its launch.  Launched: the row is recorded and the enclosing function returns WX_OK; an error is returned;
+// declined: the dispatch goes on to its next attempt.
+#define WX_ATTEMPT(call, row)                         \
+    do {                                              \
+        const int wx_r = (call);                      \
+        if (wx_r == 1) row;                           \
+        if (wx_r) return wx_r < 0 ? wx_r : WX_OK;     \
+    } while (0)
 #include <stdlib.h>
 #include <string.h>
 #include <mutex>
@@ -147,17 +164,13 @@ __global__ __launch_bounds__(256) void k_inv1d_level(const T *__restrict__ src, 
 // outputs pairs' worth of input (2 WX_LT samples plus the F - 1 wrap-around halo on both sides, coalesced 8-byte runs),
 // and every thread computes its pairs out of LDS -- the per-level kernels above read their 2 F taps per pair through
 // L1 (8 x the bytes of the output for F = 8) and stop at 3.5 TB/s.  Same arithmetic and tap order as k_fwd1d_level /
-// k_inv1d_level.  Used for the top levels of signals of 16384 samples and more (wx_dev_wpt1d / wx_dev_iwpt1d).
+// k_inv1d_level.  Used for the top levels of long signals that the multi-level passes of wx_toptile.h do not take: wpd with more than
+// four of them (wx_dev_wpd1d) and full trees in place (the d0 > 0 blocks of wx_dev_wpt1d / wx_dev_iwpt1d).
 constexpr int WX_LT = 2048;                                  // output pairs per tile
 
-// Split form (the pyramid of a long signal, wx_dev_dwt_long / wx_dev_idwt_long): the detail half lives elsewhere -- forward:
-// approximations to dst, details to dst2; inverse: approximations from src, details from src2 (each with its own stride
-// between signals); src2 / dst2 = nullptr: the two halves are one array as above.
 template <typename T, bool INVERSE>
 __global__ __launch_bounds__(256) void k_level1_tile(const T *__restrict__ src, T *__restrict__ dst, int np, int nper,
-                                                     int64_t src_stride, int64_t dst_stride, WxFilt filt,
-                                                     const T *__restrict__ src2 = nullptr, int64_t src2_stride = 0,
-                                                     T *__restrict__ dst2 = nullptr, int64_t dst2_stride = 0)
+                                                     int64_t src_stride, int64_t dst_stride, WxFilt filt)
 {
     extern __shared__ __attribute__((aligned(16))) char wx_smem[];
     T *buf = reinterpret_cast<T *>(wx_smem);
@@ -169,8 +182,8 @@ __global__ __launch_bounds__(256) void k_level1_tile(const T *__restrict__ src, 
     const int64_t jn = node - sig * nper;
     const T *v = src + sig * src_stride + jn * (int64_t)np;
     T *o = dst + sig * dst_stride + jn * (int64_t)np;
-    const T *vd = src2 ? src2 + sig * src2_stride + jn * (int64_t)np : v + (np >> 1);      // details in (inverse)
-    T *od = dst2 ? dst2 + sig * dst2_stride + jn * (int64_t)np : o + (np >> 1);           // details out (forward)
+    const T *vd = v + (np >> 1);                                        // details in (inverse)
+    T *od = o + (np >> 1);                                              // details out (forward)
     if (!INVERSE) {
         // inputs 2 t0 - (F - 2) .. 2 t0 + 2 WX_LT + F - 2 (mod np): buf[e] = v[(2 t0 - (F - 2) + e) mod np]
         const int cnt = 2 * WX_LT + 2 * F - 3;
@@ -216,16 +229,15 @@ __global__ __launch_bounds__(256) void k_level1_tile(const T *__restrict__ src, 
 // one full level of every node of np samples (np a multiple of 2 WX_LT): nper nodes per signal, `nsig` signals
 template <typename T, bool INVERSE>
 static int launch_level1_tile(const T *src, T *dst, int64_t np, int64_t nper, int64_t nsig, int64_t src_stride, int64_t dst_stride,
-                              const WxFilt &filt, hipStream_t st, const T *src2 = nullptr, int64_t src2_stride = 0, T *dst2 = nullptr,
-                              int64_t dst2_stride = 0)
+                              const WxFilt &filt, hipStream_t st)
 {
     const int64_t grid = nper * nsig * ((np >> 1) / WX_LT);
     if (grid <= 0 || grid > 0x7fffffff) return wx_set_error(WX_EUNSUPPORTED, "tiled level: grid too large");
     const size_t lds = sizeof(T) * (size_t)(2 * WX_LT + 2 * WX_MAXF + 4);
     WX_DWT1D_TRACE(WX_R1_L1TILE, INVERSE, sizeof(T), np, wx_dwt1d_trace_take_depth(), 1, nsig, filt.F, (int)nper, src_stride != np, dst_stride != np,
-                   src2 != nullptr, dst2 != nullptr, 256u, (unsigned)grid, lds);
+                   0, 0, 256u, (unsigned)grid, lds);
     hipLaunchKernelGGL((k_level1_tile<T, INVERSE>), dim3((unsigned)grid), dim3(256), lds, st, src, dst, (int)np, (int)nper, src_stride,
-                       dst_stride, filt, src2, src2_stride, dst2, dst2_stride);
+                       dst_stride, filt);
     WX_HIP_CHECK(hipGetLastError());
     return WX_OK;
 }
@@ -1315,11 +1327,9 @@ int wx_dev_iwpt1d_thresh(const T *xw, T *xh, int64_t n, int L, int64_t batch, co
     WX_DWT1D_TRACE_DEPTH(0);
     if constexpr (sizeof(T) == 8) {
         // leaves of a tree (denoiseall(:wpt), Denoising.jl:527): the threshold rides on the loads of the tree-driven lattice inverse
-        if (status && !wx_skip_register_kernels()) {
-            const int r = wx_lattice_tree_f64(true, (const double *)xw, (double *)xh, n, L, batch, n, 0, filt, status, nstatus, st, &thr);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, 0, thr.t || thr.head, 0, 0);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (status && !wx_skip_register_kernels())
+            WX_ATTEMPT(wx_lattice_tree_f64(true, (const double *)xw, (double *)xh, n, L, batch, n, 0, filt, status, nstatus, st, &thr),
+                       WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, 0, thr.t || thr.head, 0, 0));
     }
     WX_DWT1D_TRACE_DEPTH(L);
     return launch_inv_fused<T>(xw, xh, n, L, batch, n, n, filt, status, nstatus, nullptr, 0, st, thr);
@@ -1344,19 +1354,15 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     const int64_t ys = n * (L + 1);
     if constexpr (sizeof(T) == 8) {
         // 4096-sample signals: rotations in registers, every level leaves through an LDS transposition (wx_lattice.hip)
-        if (!force_generic && !wx_skip_register_kernels()) {
-            const int r = wx_lattice_wpd_f64((const double *)x, (double *)y, n, L, batch, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F));
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (!force_generic && !wx_skip_register_kernels())
+            WX_ATTEMPT(wx_lattice_wpd_f64((const double *)x, (double *)y, n, L, batch, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F)));
     }
     if constexpr (sizeof(T) == 4) {
         // short Float32 signals: the interleaved lattice wpd kernel with Float32 at the two ends (wx_lattice_sgw.hip)
-        if (!force_generic && !wx_skip_register_kernels() && n <= 128) {        // 256 samples: the fused LDS kernel is as fast (0.47-0.58 against 0.44-0.50)
-            const int r = wx_lattice_wpd_g_f32((const float *)x, (float *)y, n, L, batch, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F));
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (!force_generic && !wx_skip_register_kernels() && n <= 128)          // 256 samples: the fused LDS kernel is as fast (0.47-0.58 against 0.44-0.50)
+            WX_ATTEMPT(wx_lattice_wpd_g_f32((const float *)x, (float *)y, n, L, batch, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATWPD, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F)));
     }
     if (!force_generic && wx_fused1d_ok<T>(n, filt.F))
         return launch_fwd_fused<T, true>(x, y, n, L, batch, n, ys, filt, nullptr, 0, st);
@@ -1404,6 +1410,33 @@ int wx_dev_wpd1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     return WX_OK;
 }
 
+// The plan of a long full tree out of place (wx_dev_wpt1d / wx_dev_iwpt1d; n a power of two above 4096, wx_top_levels_ok(filt.F)): the
+// top d0 levels run up to four per pass through LDS (wx_toptile.h: Ltop = min(L, d0) levels in npass passes); at depth d0 every node is
+// an independent signal of n2 samples that the lattice kernels (lat: n2 = 4096, d0 = dl = log2(n / 4096)) or the fused LDS kernel (the
+// longest signal a CU's LDS holds) take.  d0 < 1: the path does not apply.
+struct WxLongFull { int dl; bool lat; int64_t n2; int d0, Ltop, npass; };
+template <typename T> static WxLongFull wx_long_full_plan(bool inverse, int64_t n, int L, int64_t in_stride, const WxFilt &filt, bool noreg)
+{
+    WxLongFull p;
+    p.dl = 0;
+    while (((int64_t)4096 << p.dl) < n) ++p.dl;
+    p.lat = !noreg && L - p.dl >= 6 && n < ((int64_t)1 << 30);
+    if constexpr (sizeof(T) == 8) p.lat = p.lat && wx_lattice_applicable_f64(filt);
+    p.n2 = 4096;
+    if (!p.lat) { p.n2 = n; while (p.n2 > 2 && !wx_fused1d_ok<T>(p.n2, filt.F)) p.n2 >>= 1; }
+    p.d0 = 0;
+    while ((p.n2 << p.d0) < n) ++p.d0;
+    // at most four levels: ONE tiled pass whatever the length of the nodes it leaves (until round 5 the levels below the longest node a
+    // CU's LDS holds went to the fused kernel: two passes, 0.87-0.93 ms per GiB for a full tree of depth 4 on 8192 ... 65536 samples)
+    // (the inverse only where the fused kernel does not take the whole signal in one pass: its single pass is faster -- 8192 Float64
+    // samples 0.52 against 0.61 ms per GiB, 16384 Float32 samples 0.55 against 0.75)
+    if (L <= 4 && p.d0 < L && (p.d0 >= 1 || !inverse)) p.d0 = L;
+    if (inverse && in_stride != n && p.d0 < L) p.d0 = -1;                 // strided leaves and more than one kernel: not here
+    p.Ltop = L < p.d0 ? L : p.d0;
+    p.npass = (p.Ltop + 3) / 4;
+    return p;
+}
+
 // wpt: y is (n, batch).  status == nullptr -> full tree of depth L.  scratch: n*batch elements
 // (only touched on the generic path when L > 1).
 template <typename T>
@@ -1417,24 +1450,24 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
         return WX_OK;
     }
     const bool noreg = wx_skip_register_kernels();      // test hook: fused LDS kernels only
+    const bool reg_full = !force_generic && !noreg && !status;      // the gate of every register kernel for full trees
     if constexpr (sizeof(T) == 4) {
         // Float32 full trees of 128 / 256 samples (the columns of 128- / 256-row images arrive here too): the masked tree kernels in Float32
         // arithmetic on pairs of signals, as a tree of ones (wx_lattice_tree_s.h; policy and numbers: api_wpt1d)
-        if (!force_generic && !noreg && !status && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && x != y && batch >= 2 * 4096 / n) {
+        if (reg_full && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && x != y && batch >= 2 * 4096 / n) {
             const uint8_t *ones = wx_full_tree_ones(st);
-            if (ones) {
-                const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0);
-                if (r) return r < 0 ? r : WX_OK;
-            }
+            if (ones)
+                WX_ATTEMPT(wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st),
+                           WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0));
         }
+        // Float32 full trees on the lattice kernels (wx_lattice_f32.hip): 4096 samples with Float32 at the two ends, 64 .. 2048 samples
+        // interleaved.  Ahead of the lane tree, after the tree of ones (the inverse has that one behind); what it declines is a function
+        // of these arguments alone, so one attempt serves every length.
+        if (reg_full)
+            WX_ATTEMPT(wx_lattice_f32(false, (const float *)x, (float *)y, n, L, batch, n, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATF32, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), 0, 0));
         // very short Float32 signals, full tree (the columns of small images arrive here too): one lane per signal (wx_lanetree.h)
-        if (!force_generic && !noreg && !status && n <= 128) {
-            const int r = wx_lattice_f32(false, (const float *)x, (float *)y, n, L, batch, n, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), 0, 0);
-            if (r) return r < 0 ? r : WX_OK;
-        }
-        if (!force_generic && !noreg && !status && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && x != y) {
+        if (reg_full && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && x != y) {
             WxLaneTree lt;
             for (int i = 0; i < 8; ++i) lt.bits[i] = 0xffffffffu;
             WX_DWT1D_TRACE(WX_R1_LANETREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1);
@@ -1444,44 +1477,22 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
     if constexpr (sizeof(T) == 8) {
         // full tree: rotations in registers (wx_lattice.hip; Haar is the lattice with one rotation: 0.78 ms against the
         // 0.94 ms of the Walsh-Hadamard kernel at the target's size)
-        if (!force_generic && !noreg && !status) {
-            const int r = wx_lattice_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF64, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (reg_full)
+            WX_ATTEMPT(wx_lattice_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATF64, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0));
         // Haar where the lattice does not apply (depths below 6, ...): Walsh-Hadamard formulation (wx_haar.hip)
-        if (!force_generic && !noreg && !status) {
-            const int r = wx_haar_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_HAAR, 0, sizeof(T), n, 0, L, batch, filt.F);
-            if (r) return r < 0 ? r : WX_OK;
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        // Float32 signals of 4096 samples, full tree: the lattice kernels with Float32 at the two ends (wx_lattice_f32.hip)
-        if (!force_generic && !noreg && !status) {
-            const int r = wx_lattice_f32(false, (const float *)x, (float *)y, n, L, batch, n, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 0, sizeof(T), n, 0, L, batch, filt.F, wx_lat_stages(filt.F), 0, 0);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (reg_full)
+            WX_ATTEMPT(wx_haar_wpt_f64((const double *)x, (double *)y, n, L, batch, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_HAAR, 0, sizeof(T), n, 0, L, batch, filt.F));
     }
     // Long signals, full tree: the top levels up to four per pass through LDS (wx_toptile.h; one pass per level until round 4),
     // after which every node is an independent signal -- contiguous, (n2, batch << d0) in Julia layout -- that the lattice
     // kernels (n2 = 4096) or the fused LDS kernel (the longest signal a CU's LDS holds) finish at their own rate.
     if (!force_generic && !status && x != y && wx_is_pow2(n) && n > 4096 && wx_top_levels_ok(filt.F)) {
-        int dl = 0;
-        while (((int64_t)4096 << dl) < n) ++dl;
-        bool lat = !noreg && L - dl >= 6 && n < ((int64_t)1 << 30);
-        if constexpr (sizeof(T) == 8) lat = lat && wx_lattice_applicable_f64(filt);
-        int64_t n2 = 4096;
-        if (!lat) { n2 = n; while (n2 > 2 && !wx_fused1d_ok<T>(n2, filt.F)) n2 >>= 1; }
-        int d0 = 0;
-        while ((n2 << d0) < n) ++d0;
-        // at most four levels: ONE tiled pass whatever the length of the nodes it leaves (until round 5 the levels below the longest node a
-        // CU's LDS holds went to the fused kernel: two passes, 0.87-0.93 ms per GiB for a full tree of depth 4 on 8192 ... 65536 samples)
-        if (L <= 4 && d0 < L) d0 = L;
-        if (d0 >= 1 && wx_fused1d_ok<T>(lat ? 4096 : n2, filt.F) && (scratch || (L <= d0 && L <= 4))) {
-            const int Ltop = L < d0 ? L : d0;
-            const int npass = (Ltop + 3) / 4;
+        const WxLongFull plan = wx_long_full_plan<T>(false, n, L, n, filt, noreg);
+        const int d0 = plan.d0, Ltop = plan.Ltop, npass = plan.npass;
+        const int64_t n2 = plan.n2;
+        if (d0 >= 1 && wx_fused1d_ok<T>(n2, filt.F) && (scratch || (L <= d0 && L <= 4))) {
             // the nodes of depth Ltop land in scratch when a finishing kernel follows (it writes y), in y otherwise
             T *target = L > Ltop ? scratch : y;
             const T *src = x;
@@ -1495,77 +1506,25 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
                 src = dst;
             }
             if (L == Ltop) return WX_OK;
-            if (lat) {
-                int r;
-                if constexpr (sizeof(T) == 8)
-                    r = wx_lattice_wpt_f64((const double *)scratch, (double *)y, 4096, L - d0, batch << d0, filt, st);
-                else
-                    r = wx_lattice_f32(false, (const float *)scratch, (float *)y, 4096, L - d0, batch << d0, 4096, filt, st);
-                if (r == 1)
-                    WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 0, sizeof(T), 4096, d0, L - d0, batch << d0, filt.F, wx_lat_stages(filt.F),
-                                   wx_dwt1d_trace_take_folded(), 0);
-                if (r < 0) return r;
-                if (r == 1) return WX_OK;
-            }
+            if (plan.lat)
+                WX_ATTEMPT(wx_lattice_full_T<T>(false, scratch, y, 4096, L - d0, batch << d0, filt, st),
+                           WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 0, sizeof(T), 4096, d0, L - d0, batch << d0, filt.F,
+                                          wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0));
             WX_DWT1D_TRACE_DEPTH(d0);
             return launch_fwd_fused<T, false>(scratch, y, n2, L - d0, batch << d0, n2, n2, filt, nullptr, 0, st);
         }
     }
-    {
-        // Longer signals, full tree: after d0 = log2(n / 4096) levels every node is an independent 4096-sample signal --
-        // contiguous, (4096, batch << d0) in Julia layout -- which the lattice kernels finish at their own rate.  The top
-        // levels are one pass each (the fused LDS kernel with L = 1 while the node fits a CU, the per-level kernel above
-        // that); n = 8192, L = 11: 2.32 -> 1.6 ms for 32768 signals.
-        int dl = 0;
-        while (((int64_t)4096 << dl) < n) ++dl;
-        if (!force_generic && !noreg && !status && scratch && dl >= 1 && dl <= 4 && n == ((int64_t)4096 << dl) && L - dl >= 6 &&
-            x != y && wx_lattice_applicable_f64(filt)) {
-            const T *src = x;
-            for (int d = 0; d < dl; ++d) {
-                T *dst = ((dl - 1 - d) & 1) ? y : scratch;             // depth dl lands in scratch
-                const int64_t nd = n >> d;
-                int rc = WX_OK;
-                WX_DWT1D_TRACE_DEPTH(d);
-                if (wx_fused1d_ok<T>(nd, filt.F))
-                    rc = launch_fwd_fused<T, false>(src, dst, nd, 1, batch << d, nd, nd, filt, nullptr, 0, st);
-                else
-                    rc = launch_level1_tile<T, false>(src, dst, nd, (int64_t)1 << d, batch, n, n, filt, st);
-                if (rc) return rc;
-                src = dst;
-            }
-            int r;
-            if constexpr (sizeof(T) == 8)
-                r = wx_lattice_wpt_f64((const double *)scratch, (double *)y, 4096, L - dl, batch << dl, filt, st);
-            else
-                r = wx_lattice_f32(false, (const float *)scratch, (float *)y, 4096, L - dl, batch << dl, 4096, filt, st);
-            if (r == 1)
-                WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 0, sizeof(T), 4096, dl, L - dl, batch << dl, filt.F, wx_lat_stages(filt.F),
-                               wx_dwt1d_trace_take_folded(), 0);
-            if (r < 0) return r;
-            if (r == 1) return WX_OK;
-            WX_DWT1D_TRACE_DEPTH(dl);
-            // not taken after all (alignment): the top levels are in scratch, finish with the fused kernel below
-            return launch_fwd_fused<T, false>(scratch, y, 4096, L - dl, batch << dl, 4096, 4096, filt, nullptr, 0, st);
-        }
-    }
-    {
-        // a tree (bestbasistree, maketree(:dwt), ...): the lattice computes every node in registers, the tree decides which
-        // lines leave after which level (wx_lattice_tree.h; Float32 signals since round 4: wx_lattice_tree32.h)
-        if (!force_generic && !noreg && status) {
-            const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, status, nstatus, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 0, 0, 0, 0, 0);
-            if (r) return r < 0 ? r : WX_OK;
-        }
-        // a full tree nothing above took, as a tree
-        if (!force_generic && !noreg && !status && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 &&
-            wx_lattice_tree_applicable_T<T>(n, filt)) {
-            const uint8_t *ones = wx_full_tree_ones(st);
-            if (ones) {
-                const int r = wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0);
-                if (r) return r < 0 ? r : WX_OK;
-            }
-        }
+    // a tree (bestbasistree, maketree(:dwt), ...): the lattice computes every node in registers, the tree decides which
+    // lines leave after which level (wx_lattice_tree.h; Float32 signals since round 4: wx_lattice_tree32.h)
+    if (!force_generic && !noreg && status)
+        WX_ATTEMPT(wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, status, nstatus, st),
+                   WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 0, 0, 0, 0, 0));
+    // a full tree nothing above took, as a tree
+    if (reg_full && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 && wx_lattice_tree_applicable_T<T>(n, filt)) {
+        const uint8_t *ones = wx_full_tree_ones(st);
+        if (ones)
+            WX_ATTEMPT(wx_lattice_tree_T<T>(false, x, y, n, L, batch, n, 0, filt, ones, ((int64_t)1 << L) - 1, st),
+                       WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), n, 0, L, batch, filt.F, 1, 0, 0, 0, 0));
     }
     if (!force_generic && wx_fused1d_ok<T>(n, filt.F))
         return launch_fwd_fused<T, false>(x, y, n, L, batch, n, n, filt, status, nstatus, st);
@@ -1628,24 +1587,25 @@ int wx_dev_wpt1d(const T *x, T *y, int64_t n, int L, int64_t batch, const WxFilt
 // A pyramid only ever splits its approximation: level d reads the n >> d approximation samples and writes n >> (d + 1)
 // approximations and as many details, so the whole transform moves 2 n (1 + 1/2 + 1/4 + ...) < 4 n samples.  The per-level
 // kernels for trees (k_fwd1d_level, one launch per level over the WHOLE signal) moved 2 n L: 13 ms for 65536 x 4096 samples'
-// worth of 16384-sample signals (4 % of the HBM peak).  Here: the top dl levels are one tiled pass each on the approximation
-// (k_level1_tile, details straight to their final place, approximations ping-pong in scratch), and from 4096 samples on the
-// tree-driven lattice kernel finishes the pyramid reading / writing with the long signal's stride.
+// worth of 16384-sample signals (4 % of the HBM peak).  Here: the top dl levels run up to four per tiled pass on the approximation
+// (wx_toptile.h, details straight to their final place, the approximation that is split further in scratch), and from 4096 samples on
+// the tree-driven lattice kernel finishes the pyramid reading / writing with the long signal's stride.
 // the length the tiled top levels stop at (0: the long-signal path does not apply) and who finishes: the lattice kernels at 4096
 // samples (Float64, filters the lattice factors), otherwise the fused LDS kernel at the longest signal that fits a CU's LDS
 // (8192 Float64 / 16384 Float32 samples)
 template <typename T> static int64_t wx_dwt_long_plan(int64_t n, const WxFilt &filt, bool *lattice)
 {
     *lattice = false;
+    // the top levels are tiled passes of wx_toptile.h (both finishers want a filter those are built for: an even length up to 20 taps)
+    if (!wx_top_levels_ok(filt.F)) return 0;
     if (!wx_is_pow2(n) || n > ((int64_t)1 << 24)) return 0;
     // 8192 samples (and, Float32, 16384) fit the fused LDS kernel, but one top pass + the lattice pyramid on the approximation
     // moves 3 n samples at memory speed (Float64 8192 samples: 1.38 -> 1.2 ms per 2 GiB)
-    if (n >= 8192 && wx_top_levels_ok(filt.F) && !wx_skip_register_kernels() && wx_lattice_tree_applicable_T<T>(4096, filt)) {
+    if (n >= 8192 && !wx_skip_register_kernels() && wx_lattice_tree_applicable_T<T>(4096, filt)) {
         *lattice = true;
         return 4096;
     }
     if (wx_fused1d_ok<T>(n, filt.F)) return 0;
-    if (n >= 16384 && !wx_skip_register_kernels() && wx_lattice_tree_applicable_T<T>(4096, filt)) { *lattice = true; return 4096; }
     int64_t n2 = n;
     while (n2 > 4096 && !wx_fused1d_ok<T>(n2, filt.F)) n2 >>= 1;
     return (n2 >= 4096 && n2 < n && wx_fused1d_ok<T>(n2, filt.F)) ? n2 : 0;
@@ -1670,71 +1630,34 @@ int wx_dev_dwt_long(const T *x, T *y, int64_t n, int Lp, int64_t batch, const Wx
     int dl = 0;
     while ((n2 << dl) < n) ++dl;
     int top = Lp < dl ? Lp : dl;
-    if (wx_top_levels_ok(filt.F)) {
-        if (Lp <= 4 || (Lp > dl && Lp - dl <= 2 && Lp <= 8 && (n >> 4) >= 4096)) top = Lp;       // see wx_dev_idwt_long
-        // up to four levels per pass (wx_toptile.h): the details leave at their final places in y, the approximation that is
-        // split further goes to scratch (signal stride n; passes alternate between its two halves)
-        const T *src = x;
-        int64_t cur_n = n;
-        int done = 0, pidx = 0;
-        while (done < top) {
-            const int NLp = top - done < 4 ? top - done : 4;
-            const bool more = done + NLp < top || Lp > top;
-            T *deep = scratch + ((pidx & 1) ? n / 2 : 0);
-            unsigned split = 0;
-            for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);           // heap nodes 1, 2, 4, 8: the approximation branch
-            WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), cur_n, done, NLp, batch, filt.F, NLp, (int)split, 1, cur_n != n, more ? 1 : 0);
-            const int rc = wx_dev_top_levels<T>(false, src, y, deep, cur_n, NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
-            if (rc) return rc;
-            src = deep;
-            cur_n >>= NLp;
-            done += NLp;
-            ++pidx;
-        }
-        if (Lp > top) {
-            {
-                if (lattice) {
-                    const int r = wx_lattice_tree_T<T>(false, src, y, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
-                                                      nullptr, n);
-                    if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, Lp - dl, batch, filt.F, 0, 0, 0, n != 4096, n != 4096);
-                    if (r < 0) return r;
-                    if (r == 1) return WX_OK;
-                    if (!wx_fused1d_ok<T>(n2, filt.F)) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: more than 2^31 - 1 signals in one call");
-                }
-            }
-            WX_DWT1D_TRACE_DEPTH(dl);
-            return launch_fwd_fused<T, false>(src, y, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, st);
-        }
-        return WX_OK;
-    }
-    const int64_t S = n / 2 + n / 4;                           // scratch per signal: approximations of odd / even depth
-    T *bufs[2] = {scratch, scratch + n / 2};
+    if (Lp <= 4 || (Lp > dl && Lp - dl <= 2 && Lp <= 8 && (n >> 4) >= 4096)) top = Lp;       // see wx_dev_idwt_long
+    // up to four levels per pass (wx_toptile.h; a plan means wx_top_levels_ok(filt.F)): the details leave at their final places in y,
+    // the approximation that is split further goes to scratch (signal stride n; passes alternate between its two halves)
     const T *src = x;
-    int64_t src_stride = n;
-    for (int d = 0; d < top; ++d) {
-        const int64_t np = n >> d;
-        WX_DWT1D_TRACE_DEPTH(d);
-        const int rc = launch_level1_tile<T, false>(src, bufs[d & 1], np, 1, batch, src_stride, S, filt, st, nullptr, 0, y + (np >> 1), n);
+    int64_t cur_n = n;
+    int done = 0, pidx = 0;
+    while (done < top) {
+        const int NLp = top - done < 4 ? top - done : 4;
+        const bool more = done + NLp < top || Lp > top;
+        T *deep = scratch + ((pidx & 1) ? n / 2 : 0);
+        unsigned split = 0;
+        for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);           // heap nodes 1, 2, 4, 8: the approximation branch
+        WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), cur_n, done, NLp, batch, filt.F, NLp, (int)split, 1, cur_n != n, more ? 1 : 0);
+        const int rc = wx_dev_top_levels<T>(false, src, y, deep, cur_n, NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
         if (rc) return rc;
-        src = bufs[d & 1];
-        src_stride = S;
+        src = deep;
+        cur_n >>= NLp;
+        done += NLp;
+        ++pidx;
     }
-    if (Lp > top) {
-        {
-            if (lattice) {
-                const int r = wx_lattice_tree_T<T>(false, src, y, 4096, Lp - dl, batch, S, 0, filt, status, nstatus, st,
-                                                  nullptr, n);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, Lp - dl, batch, filt.F, 0, 0, 0, n != 4096, S != 4096);
-                if (r < 0) return r;
-                if (r == 1) return WX_OK;
-                if (!wx_fused1d_ok<T>(n2, filt.F)) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: more than 2^31 - 1 signals in one call");
-            }
-        }
-        WX_DWT1D_TRACE_DEPTH(dl);
-        return launch_fwd_fused<T, false>(src, y, n2, Lp - dl, batch, S, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, st);
+    if (Lp == top) return WX_OK;
+    if (lattice) {
+        WX_ATTEMPT(wx_lattice_tree_T<T>(false, src, y, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st, nullptr, n),
+                   WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, Lp - dl, batch, filt.F, 0, 0, 0, n != 4096, n != 4096));
+        if (!wx_fused1d_ok<T>(n2, filt.F)) return wx_set_error(WX_EUNSUPPORTED, "dwt of a long signal: more than 2^31 - 1 signals in one call");
     }
-    WX_HIP_CHECK(hipMemcpy2DAsync(y, n * sizeof(T), src, S * sizeof(T), (n >> top) * sizeof(T), batch, hipMemcpyDeviceToDevice, st));
-    return WX_OK;
+    WX_DWT1D_TRACE_DEPTH(dl);
+    return launch_fwd_fused<T, false>(src, y, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, st);
 }
 
 template <typename T>
@@ -1749,79 +1672,40 @@ int wx_dev_idwt_long(const T *xw, T *y, int64_t n, int Lp, int64_t batch, const 
     int dl = 0;
     while ((n2 << dl) < n) ++dl;
     int top = Lp < dl ? Lp : dl;
-    if (wx_top_levels_ok(filt.F)) {
-        // a shallow pyramid, or one that leaves only a level or two for the finishing kernel (which is slow or not applicable
-        // there: idwtall of 32768-sample signals with L = 4 took 9.8 ms in round 3), runs entirely in the top passes
-        // (the top passes apply neither denoise()'s threshold nor the rebuilt head of the lane-local tail: only without them)
-        if (!thr.t && !thr.head && (Lp <= 4 || (Lp > dl && Lp - dl <= 2 && Lp <= 8 && (n >> 4) >= 4096))) top = Lp;   // every pass's input is at least a tile long
-        // mirror of wx_dev_dwt_long: the lattice (or fused) inverse rebuilds the approximation of depth `top` in scratch, then up to
-        // four synthesis levels per pass, the details coming straight from xw
-        const int npass = (top + 3) / 4;
-        auto buf = [&](int p) -> T * { return scratch + ((p & 1) ? n / 2 : 0); };
-        if (Lp > top) {
-            T *cur = buf(npass - 1);
-            bool done = false;
-            {
-                if (lattice) {
-                    const int r = wx_lattice_tree_T<T>(true, xw, cur, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
-                                                      &thr, n);
-                    if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, Lp, Lp - dl, batch, filt.F, 0, 0, thr.t || thr.head, n != 4096, n != 4096);
-                    if (r < 0) return r;
-                    done = r == 1;
-                    if (!done && !wx_fused1d_ok<T>(n2, filt.F))
-                        return wx_set_error(WX_EUNSUPPORTED, "idwt of a long signal: more than 2^31 - 1 signals in one call");
-                }
-            }
-            if (!done) {
-                WX_DWT1D_TRACE_DEPTH(Lp);
-                const int rc = launch_inv_fused<T>(xw, cur, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, nullptr, 0,
-                                                   st, thr);
-                if (rc) return rc;
-            }
-        }
-        for (int p = npass - 1; p >= 0; --p) {
-            const int NLp = top - 4 * p < 4 ? top - 4 * p : 4;
-            const bool more = p < npass - 1 || Lp > top;
-            unsigned split = 0;
-            for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);
-            T *dst = p == 0 ? y : buf(p - 1);
-            WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n >> (4 * p), 4 * p + NLp, NLp, batch, filt.F, NLp, (int)split, 1, p != 0, more ? 1 : 0);
-            const int rc = wx_dev_top_levels<T>(true, xw, dst, buf(p), n >> (4 * p), NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
-            if (rc) return rc;
-        }
-        return WX_OK;
-    }
-    const int64_t S = n / 2 + n / 4;
-    T *bufs[2] = {scratch, scratch + n / 2};
-    // the approximation of depth `top` goes where the forward left it: bufs[(top - 1) & 1]
-    T *cur = bufs[(top - 1) & 1];
+    // a shallow pyramid, or one that leaves only a level or two for the finishing kernel (which is slow or not applicable
+    // there: idwtall of 32768-sample signals with L = 4 took 9.8 ms in round 3), runs entirely in the top passes
+    // (the top passes apply neither denoise()'s threshold nor the rebuilt head of the lane-local tail: only without them)
+    if (!thr.t && !thr.head && (Lp <= 4 || (Lp > dl && Lp - dl <= 2 && Lp <= 8 && (n >> 4) >= 4096))) top = Lp;   // every pass's input is at least a tile long
+    // mirror of wx_dev_dwt_long: the lattice (or fused) inverse rebuilds the approximation of depth `top` in scratch, then up to
+    // four synthesis levels per pass, the details coming straight from xw
+    const int npass = (top + 3) / 4;
+    auto buf = [&](int p) -> T * { return scratch + ((p & 1) ? n / 2 : 0); };
     if (Lp > top) {
+        T *cur = buf(npass - 1);
         bool done = false;
-        {
-            if (lattice) {
-                const int r = wx_lattice_tree_T<T>(true, xw, cur, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st,
-                                                  &thr, S);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, Lp, Lp - dl, batch, filt.F, 0, 0, thr.t || thr.head, S != 4096, n != 4096);
-                if (r < 0) return r;
-                done = r == 1;
-                if (!done && !wx_fused1d_ok<T>(n2, filt.F))
-                    return wx_set_error(WX_EUNSUPPORTED, "idwt of a long signal: more than 2^31 - 1 signals in one call");
-            }
+        if (lattice) {
+            const int r = wx_lattice_tree_T<T>(true, xw, cur, 4096, Lp - dl, batch, n, 0, filt, status, nstatus, st, &thr, n);
+            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, Lp, Lp - dl, batch, filt.F, 0, 0, thr.t || thr.head, n != 4096, n != 4096);
+            if (r < 0) return r;
+            done = r == 1;
+            if (!done && !wx_fused1d_ok<T>(n2, filt.F))
+                return wx_set_error(WX_EUNSUPPORTED, "idwt of a long signal: more than 2^31 - 1 signals in one call");
         }
         if (!done) {
             WX_DWT1D_TRACE_DEPTH(Lp);
-            const int rc = launch_inv_fused<T>(xw, cur, n2, Lp - dl, batch, n, S, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, nullptr, 0,
+            const int rc = launch_inv_fused<T>(xw, cur, n2, Lp - dl, batch, n, n, filt, status, n2 - 1 < nstatus ? n2 - 1 : nstatus, nullptr, 0,
                                                st, thr);
             if (rc) return rc;
         }
-    } else {
-        WX_HIP_CHECK(hipMemcpy2DAsync(cur, S * sizeof(T), xw, n * sizeof(T), (n >> top) * sizeof(T), batch, hipMemcpyDeviceToDevice, st));
     }
-    for (int d = top - 1; d >= 0; --d) {
-        const int64_t np = n >> d;
-        T *dst = d == 0 ? y : bufs[(d - 1) & 1];
-        WX_DWT1D_TRACE_DEPTH(d + 1);
-        const int rc = launch_level1_tile<T, true>(bufs[d & 1], dst, np, 1, batch, S, d == 0 ? n : S, filt, st, xw + (np >> 1), n);
+    for (int p = npass - 1; p >= 0; --p) {
+        const int NLp = top - 4 * p < 4 ? top - 4 * p : 4;
+        const bool more = p < npass - 1 || Lp > top;
+        unsigned split = 0;
+        for (int l = 0; l < NLp; ++l) split |= 1u << ((1 << l) - 1);
+        T *dst = p == 0 ? y : buf(p - 1);
+        WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n >> (4 * p), 4 * p + NLp, NLp, batch, filt.F, NLp, (int)split, 1, p != 0, more ? 1 : 0);
+        const int rc = wx_dev_top_levels<T>(true, xw, dst, buf(p), n >> (4 * p), NLp, batch, n, n, n, split, more ? 1u : 0u, filt, st);
         if (rc) return rc;
     }
     return WX_OK;
@@ -1838,9 +1722,9 @@ template int wx_dev_idwt_long<float>(const float *, float *, int64_t, int, int64
 // and the second needs more memory than the device has for signals of this length: what is left below reports exactly that.)
 // ---- wpt / iwpt along any tree of long signals ------------------------------------------------------------------------------
 // (what bestbasistree returns for signals of 16384 samples and more; until round 3: one launch per level over the whole signal,
-// 2-3 % of the HBM peak).  Nodes of depth d < dl = log2(n / 4096) that are split take one tiled pass (runs of consecutive split
-// nodes share a launch), children ping-pong between scratch and y at their own positions; a leaf is copied to / from its place; every
-// node of 4096 samples that is split further is one launch of the tree-driven lattice kernels with its own subtree.
+// 2-3 % of the HBM peak).  The top dl = log2(n / 4096) levels are one tiled pass through LDS (wx_toptile.h; 8192 Float64 samples: one
+// pass for the whole tree, wx_lattice_8kt.h); every node of 4096 samples that is split further is one launch of the tree-driven
+// lattice kernels with its own subtree.
 template <typename T> bool wx_wpt_long_tree_ok(int64_t n, const WxFilt &filt)
 {
     bool lattice;
@@ -1864,7 +1748,6 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
             for (int t = 1; t <= d; ++t) { const int64_t a = idx >> t; if (a - 1 >= ntree || !htree[a - 1]) return false; }
             return d < Lp && idx - 1 < ntree && htree[idx - 1] != 0;
         };
-        auto exists = [&](int d, int64_t j) { return d == 0 || split(d - 1, j >> 1); };
         // subtrees of the 4096-sample nodes that are split: one status array each (heap order from the node), uploaded together
         const int64_t NS = 4095;
         std::vector<int64_t> sub_nodes;
@@ -1891,122 +1774,52 @@ int wx_dev_wpt_long_tree(const T *x, T *y, int64_t n, int Lp, int64_t batch, con
             dsub = (const uint8_t *)wx_const_upload(hsub.data(), hsub.size(), st, true);
             if (!dsub) return WX_EHIP;
         }
-        // 8192-sample Float64 signals, inverse: ONE pass (wx_lattice_8kt.h) -- two wavefronts per signal, each rebuilds its child of the root
-        // (the masked tree kernel of its subtree, or a plain load of a leaf), the last synthesis level in direct form
+        // 8192-sample Float64 signals: ONE pass.  Inverse (wx_lattice_8kt.h): two wavefronts per signal, each rebuilds its child of the root
+        // (the masked tree kernel of its subtree, or a plain load of a leaf), the last synthesis level in direct form; forward
+        // (wx_lattice_8ktf.hip): the same, one wavefront per SIMD
         if constexpr (sizeof(T) == 8) {
-            if (inverse && n == 8192 && Lp >= 1 && split(0, 0) && (const void *)x != (const void *)y) {
+            if (n == 8192 && Lp >= 1 && split(0, 0) && (const void *)x != (const void *)y) {
                 const uint8_t *ds[2] = {nullptr, nullptr};
                 int dp[2] = {0, 0};
                 for (size_t k = 0; k < sub_nodes.size(); ++k) { ds[sub_nodes[k]] = dsub + k * NS; dp[sub_nodes[k]] = sub_depth[k]; }
-                const int r = wx_lattice_tree8k_inv_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LAT8KT, 1, sizeof(T), n, Lp, Lp, batch, filt.F, dp[0], dp[1]);
-                if (r < 0) return r;
-                if (r == 1) return WX_OK;
-            }
-            // forward: the same in one pass (wx_lattice_8ktf.hip), one wavefront per SIMD
-            if (!inverse && n == 8192 && Lp >= 1 && split(0, 0) && (const void *)x != (const void *)y) {
-                const uint8_t *ds[2] = {nullptr, nullptr};
-                int dp[2] = {0, 0};
-                for (size_t k = 0; k < sub_nodes.size(); ++k) { ds[sub_nodes[k]] = dsub + k * NS; dp[sub_nodes[k]] = sub_depth[k]; }
-                const int r = wx_lattice_tree8k_fwd_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LAT8KT, 0, sizeof(T), n, 0, Lp, batch, filt.F, dp[0], dp[1]);
-                if (r < 0) return r;
-                if (r == 1) return WX_OK;
+                if (inverse)
+                    WX_ATTEMPT(wx_lattice_tree8k_inv_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st),
+                               WX_DWT1D_TRACE(WX_R1_LAT8KT, 1, sizeof(T), n, Lp, Lp, batch, filt.F, dp[0], dp[1]));
+                else
+                    WX_ATTEMPT(wx_lattice_tree8k_fwd_f64((const double *)x, (double *)y, batch, filt, ds[0], dp[0], ds[1], dp[1], st),
+                               WX_DWT1D_TRACE(WX_R1_LAT8KT, 0, sizeof(T), n, 0, Lp, batch, filt.F, dp[0], dp[1]));
             }
         }
+        // The caller has checked wx_wpt_long_tree_ok (8192 .. 65536 samples, so dl = 1 .. 4, and a lattice plan, which wants
+        // wx_top_levels_ok(filt.F)) and hands a tree of depth Lp >= 1: the top levels are always one pass.
         const int top = Lp < dl ? Lp : dl;
-        if (wx_top_levels_ok(filt.F) && top >= 1 && top <= 4) {
-            // all top levels in one pass through LDS (wx_toptile.h): leaves leave / enter at their own places, the 4096-sample nodes
-            // that are split further pass through scratch at theirs
-            unsigned smask = 0, deepmask = 0;
-            for (int d = 0; d < top; ++d)
-                for (int64_t j = 0; j < ((int64_t)1 << d); ++j)
-                    if (split(d, j)) smask |= 1u << (((int64_t)1 << d) - 1 + j);
-            for (int64_t j : sub_nodes) deepmask |= 1u << j;
-            if (!inverse) {
-                WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), n, 0, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
-                const int rc = wx_dev_top_levels<T>(false, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
-                if (rc) return rc;
-            }
-            for (size_t k = 0; k < sub_nodes.size(); ++k) {
-                const int64_t off = sub_nodes[k] * 4096;
-                const int r = inverse ? wx_lattice_tree_T<T>(true, x + off, scratch + off, 4096, sub_depth[k], batch, n, 0,
-                                                            filt, dsub + k * NS, NS, st, nullptr, n)
-                                      : wx_lattice_tree_T<T>(false, scratch + off, y + off, 4096, sub_depth[k], batch, n, 0,
-                                                            filt, dsub + k * NS, NS, st, nullptr, n);
-                if (r == 1)
-                    WX_DWT1D_TRACE(WX_R1_LATTREE, inverse, sizeof(T), 4096, inverse ? dl + sub_depth[k] : dl, sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
-                if (r < 0) return r;
-                if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal: more than 2^31 - 1 signals in one call");
-            }
-            if (inverse) WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n, top, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
-            if (inverse) return wx_dev_top_levels<T>(true, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
-            return WX_OK;
-        }
-        // depth-d nodes live in P(d): the input / output for d = 0, then scratch, y, scratch, ... (forward) -- every node at its own
-        // positions, so a leaf's range is never touched by deeper nodes
-        auto P = [&](int d) -> T * { return (d & 1) ? scratch : y; };
-        auto copy = [&](const T *src, T *dst, int64_t off, int64_t len) {
-            return hipMemcpy2DAsync(dst + off, n * sizeof(T), src + off, n * sizeof(T), len * sizeof(T), batch, hipMemcpyDeviceToDevice, st);
-        };
+        if (!wx_top_levels_ok(filt.F) || top < 1 || top > 4)
+            return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal along a tree: 8192 .. 65536 samples, a filter of an even length up to 20 taps");
+        // all top levels in one pass through LDS (wx_toptile.h): leaves leave / enter at their own places, the 4096-sample nodes
+        // that are split further pass through scratch at theirs
+        unsigned smask = 0, deepmask = 0;
+        for (int d = 0; d < top; ++d)
+            for (int64_t j = 0; j < ((int64_t)1 << d); ++j)
+                if (split(d, j)) smask |= 1u << (((int64_t)1 << d) - 1 + j);
+        for (int64_t j : sub_nodes) deepmask |= 1u << j;
         if (!inverse) {
-            for (int d = 0; d <= top; ++d) {
-                const int64_t np = n >> d, cnt = (int64_t)1 << d;
-                const T *src = d == 0 ? x : P(d);
-                for (int64_t j = 0; j < cnt;) {
-                    if (!exists(d, j)) { ++j; continue; }
-                    if (d < top && split(d, j)) {
-                        int64_t j1 = j;
-                        while (j1 < cnt && exists(d, j1) && split(d, j1)) ++j1;
-                        WX_DWT1D_TRACE_DEPTH(d);
-                        const int rc = launch_level1_tile<T, false>(src + j * np, P(d + 1) + j * np, np, j1 - j, batch, n, n, filt, st);
-                        if (rc) return rc;
-                        j = j1;
-                        continue;
-                    }
-                    if (d == dl && Lp > dl && split(d, j)) { ++j; continue; }       // finished by the lattice below
-                    if (src != y) WX_HIP_CHECK(copy(src, y, j * np, np));            // a leaf of depth d
-                    ++j;
-                }
-            }
-            for (size_t k = 0; k < sub_nodes.size(); ++k) {
-                const int64_t off = sub_nodes[k] * 4096;
-                const int r = wx_lattice_tree_T<T>(false, (dl == 0 ? x : P(dl)) + off, y + off, 4096, sub_depth[k], batch, n,
-                                                  0, filt, dsub + k * NS, NS, st, nullptr, n);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 0, sizeof(T), 4096, dl, sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
-                if (r < 0) return r;
-                if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal: more than 2^31 - 1 signals in one call");
-            }
-            return WX_OK;
+            WX_DWT1D_TRACE(WX_R1_TOP, 0, sizeof(T), n, 0, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
+            const int rc = wx_dev_top_levels<T>(false, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
+            if (rc) return rc;
         }
-        // inverse: depth-d nodes are rebuilt into Q(d) = y for d = 0, then scratch, y, ...; leaves come from xw
-        auto Q = [&](int d) -> T * { return (d & 1) ? scratch : y; };
         for (size_t k = 0; k < sub_nodes.size(); ++k) {
             const int64_t off = sub_nodes[k] * 4096;
-            const int r = wx_lattice_tree_T<T>(true, x + off, Q(dl) + off, 4096, sub_depth[k], batch, n, 0, filt,
-                                              dsub + k * NS, NS, st, nullptr, n);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), 4096, dl + sub_depth[k], sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
+            const int r = inverse ? wx_lattice_tree_T<T>(true, x + off, scratch + off, 4096, sub_depth[k], batch, n, 0,
+                                                        filt, dsub + k * NS, NS, st, nullptr, n)
+                                  : wx_lattice_tree_T<T>(false, scratch + off, y + off, 4096, sub_depth[k], batch, n, 0,
+                                                        filt, dsub + k * NS, NS, st, nullptr, n);
+            if (r == 1)
+                WX_DWT1D_TRACE(WX_R1_LATTREE, inverse, sizeof(T), 4096, inverse ? dl + sub_depth[k] : dl, sub_depth[k], batch, filt.F, 0, 0, 0, 1, 1);
             if (r < 0) return r;
-            if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "iwpt of a long signal: more than 2^31 - 1 signals in one call");
+            if (r != 1) return wx_set_error(WX_EUNSUPPORTED, "wpt of a long signal: more than 2^31 - 1 signals in one call");
         }
-        for (int d = top; d >= 0; --d) {
-            const int64_t np = n >> d, cnt = (int64_t)1 << d;
-            for (int64_t j = 0; j < cnt;) {
-                if (!exists(d, j)) { ++j; continue; }
-                if (d < top && split(d, j)) {
-                    int64_t j1 = j;
-                    while (j1 < cnt && exists(d, j1) && split(d, j1)) ++j1;
-                    WX_DWT1D_TRACE_DEPTH(d + 1);
-                    const int rc = launch_level1_tile<T, true>(Q(d + 1) + j * np, Q(d) + j * np, np, j1 - j, batch, n, n, filt, st);
-                    if (rc) return rc;
-                    j = j1;
-                    continue;
-                }
-                if (d == dl && Lp > dl && split(d, j)) { ++j; continue; }           // rebuilt by the lattice above
-                WX_HIP_CHECK(copy(x, Q(d), j * np, np));                             // a leaf of depth d: from the input
-                ++j;
-            }
-        }
+        if (inverse) WX_DWT1D_TRACE(WX_R1_TOP, 1, sizeof(T), n, top, top, batch, filt.F, top, (int)smask, 1, 0, (int)deepmask);
+        if (inverse) return wx_dev_top_levels<T>(true, x, y, scratch, n, top, batch, n, n, n, smask, deepmask, filt, st);
         return WX_OK;
     }
 }
@@ -2041,13 +1854,12 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
         xw = scratch2;
         is = n;
     }
+    const bool reg_full = !force_generic && !noreg && !status && !colmap;      // the gate of every register kernel for full trees
     if constexpr (sizeof(T) == 4) {
-        if (!force_generic && !noreg && !status && !colmap && n <= 128) {
-            const int r = wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n);
-            if (r) return r < 0 ? r : WX_OK;
-        }
-        if (!force_generic && !noreg && !status && !colmap && is == n && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && xw != xh) {
+        if (reg_full && n <= 128)
+            WX_ATTEMPT(wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n));
+        if (reg_full && is == n && wx_small_tree_wanted<T>(n, filt.F, false, false) && n <= 128 && xw != xh) {
             WxLaneTree lt;
             for (int i = 0; i < 8; ++i) lt.bits[i] = 0xffffffffu;
             WX_DWT1D_TRACE(WX_R1_LANETREE, 1, sizeof(T), n, L, L, batch, filt.F, 1);
@@ -2055,33 +1867,26 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
         }
     }
     if constexpr (sizeof(T) == 8) {
-        if (!force_generic && !noreg && !status && !colmap) {
-            const int r = wx_lattice_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, is, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF64, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), is != n);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (reg_full)
+            WX_ATTEMPT(wx_lattice_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, is, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATF64, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), is != n));
         // Haar where the lattice does not apply, dense leaves: inverse Walsh-Hadamard formulation (wx_haar.hip)
-        if (!force_generic && !noreg && !status && !colmap && is == n) {
-            const int r = wx_haar_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_HAAR, 1, sizeof(T), n, L, L, batch, filt.F);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (reg_full && is == n)
+            WX_ATTEMPT(wx_haar_iwpt_f64((const double *)xw, (double *)xh, n, L, batch, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_HAAR, 1, sizeof(T), n, L, L, batch, filt.F));
     }
     if constexpr (sizeof(T) == 4) {
-        if (!force_generic && !noreg && !status && !colmap && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && xw != xh &&
-            batch >= 2 * 4096 / n) {
+        // the tree of ones BEHIND the lane tree and the first wx_lattice_f32 (the forward has it ahead of both: 128 samples, L >= 2, up
+        // to 8 taps can end in different kernels in the two directions; each direction keeps its order)
+        if (reg_full && (n == 256 || (n == 128 && L >= 2)) && filt.F <= 8 && xw != xh && batch >= 2 * 4096 / n) {
             const uint8_t *ones = wx_full_tree_ones(st);
-            if (ones) {
-                const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n);
-                if (r) return r < 0 ? r : WX_OK;
-            }
+            if (ones)
+                WX_ATTEMPT(wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st),
+                           WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n));
         }
-        if (!force_generic && !noreg && !status && !colmap) {
-            const int r = wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n);
-            if (r) return r < 0 ? r : WX_OK;
-        }
+        if (reg_full)
+            WX_ATTEMPT(wx_lattice_f32(true, (const float *)xw, (float *)xh, n, L, batch, is, filt, st),
+                       WX_DWT1D_TRACE(WX_R1_LATF32, 1, sizeof(T), n, L, L, batch, filt.F, wx_lat_stages(filt.F), 0, is != n));
     }
     // mirror of the long-signal path of wx_dev_wpt1d: the finishing kernels rebuild the nodes of depth d0 (the lattice inverse
     // on 4096-sample nodes, or the fused LDS kernel), then the top levels up to four per pass (wx_toptile.h)
@@ -2089,35 +1894,18 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
     // pass: the pass takes the stride of its input, the finishing kernels want (node, signal) contiguous)
     if (!force_generic && !status && !colmap && (is == n || (L <= 4 && is > n && !(is & 1))) && xw != xh && wx_is_pow2(n) && n > 4096 &&
         wx_top_levels_ok(filt.F)) {
-        int dl = 0;
-        while (((int64_t)4096 << dl) < n) ++dl;
-        bool lat = !noreg && L - dl >= 6 && n < ((int64_t)1 << 30);
-        if constexpr (sizeof(T) == 8) lat = lat && wx_lattice_applicable_f64(filt);
-        int64_t n2 = 4096;
-        if (!lat) { n2 = n; while (n2 > 2 && !wx_fused1d_ok<T>(n2, filt.F)) n2 >>= 1; }
-        int d0 = 0;
-        while ((n2 << d0) < n) ++d0;
-        // at most four levels: ONE tiled pass whatever the length of the nodes it leaves (until round 5 the levels below the longest node a
-        // CU's LDS holds went to the fused kernel: two passes, 0.87-0.93 ms per GiB for a full tree of depth 4 on 8192 ... 65536 samples)
-        // (the inverse only where the fused kernel does not take the whole signal in one pass: its single pass is faster -- 8192 Float64
-        // samples 0.52 against 0.61 ms per GiB, 16384 Float32 samples 0.55 against 0.75)
-        if (L <= 4 && d0 >= 1 && d0 < L) d0 = L;
-        if (is != n && d0 < L) d0 = -1;                      // strided leaves and more than one kernel: not here
-        if (d0 >= 1 && wx_fused1d_ok<T>(lat ? 4096 : n2, filt.F) && (scratch || (L <= d0 && L <= 4))) {
-            const int Ltop = L < d0 ? L : d0;
-            const int npass = (Ltop + 3) / 4;
+        const WxLongFull plan = wx_long_full_plan<T>(true, n, L, is, filt, noreg);
+        const int d0 = plan.d0, Ltop = plan.Ltop, npass = plan.npass;
+        const int64_t n2 = plan.n2;
+        if (d0 >= 1 && wx_fused1d_ok<T>(n2, filt.F) && (scratch || (L <= d0 && L <= 4))) {
             // pass p (npass-1 .. 0) writes buffer B(p): xh for p = 0, then scratch, xh, ...; the finishing kernels write B(npass)
             auto B = [&](int p) -> T * { return (p & 1) ? scratch : xh; };
             const T *src = xw;
             if (L > Ltop) {
                 T *first = B(npass);
                 bool done = false;
-                if (lat) {
-                    int r;
-                    if constexpr (sizeof(T) == 8)
-                        r = wx_lattice_iwpt_f64((const double *)xw, (double *)first, 4096, L - d0, batch << d0, 4096, filt, st);
-                    else
-                        r = wx_lattice_f32(true, (const float *)xw, (float *)first, 4096, L - d0, batch << d0, 4096, filt, st);
+                if (plan.lat) {
+                    const int r = wx_lattice_full_T<T>(true, xw, first, 4096, L - d0, batch << d0, filt, st);
                     if (r == 1)
                         WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 1, sizeof(T), 4096, L, L - d0, batch << d0, filt.F,
                                        wx_lat_stages(filt.F), wx_dwt1d_trace_take_folded(), 0);
@@ -2143,59 +1931,17 @@ int wx_dev_iwpt1d(const T *xw, T *xh, int64_t n, int L, int64_t batch, const WxF
             return WX_OK;
         }
     }
-    {
-        // mirror of the long-signal path of wx_dev_wpt1d: the lattice inverse on the 4096-sample nodes of depth dl, then dl
-        // synthesis levels of one pass each
-        int dl = 0;
-        while (((int64_t)4096 << dl) < n) ++dl;
-        if (!force_generic && !noreg && !status && !colmap && is == n && scratch && dl >= 1 && dl <= 4 &&
-            n == ((int64_t)4096 << dl) && L - dl >= 6 && xw != xh && wx_lattice_applicable_f64(filt)) {
-            T *first = (dl & 1) ? scratch : xh;                        // as if depth dl were one more level of the ping-pong
-            int r;
-            if constexpr (sizeof(T) == 8)
-                r = wx_lattice_iwpt_f64((const double *)xw, (double *)first, 4096, L - dl, batch << dl, 4096, filt, st);
-            else
-                r = wx_lattice_f32(true, (const float *)xw, (float *)first, 4096, L - dl, batch << dl, 4096, filt, st);
-            if (r == 1)
-                WX_DWT1D_TRACE(sizeof(T) == 8 ? WX_R1_LATF64 : WX_R1_LATF32, 1, sizeof(T), 4096, L, L - dl, batch << dl, filt.F, wx_lat_stages(filt.F),
-                               wx_dwt1d_trace_take_folded(), 0);
-            if (r < 0) return r;
-            if (r == 1) {
-                const T *src2 = first;
-                for (int d = dl - 1; d >= 0; --d) {
-                    T *dst = (d & 1) ? scratch : xh;
-                    const int64_t nd = n >> d;
-                    int rc = WX_OK;
-                    WX_DWT1D_TRACE_DEPTH(d + 1);
-                    if (wx_fused1d_ok<T>(nd, filt.F))
-                        rc = launch_inv_fused<T>(src2, dst, nd, 1, batch << d, nd, nd, filt, nullptr, 0, nullptr, 0, st);
-                    else
-                        rc = launch_level1_tile<T, true>(src2, dst, nd, (int64_t)1 << d, batch, n, n, filt, st);
-                    if (rc) return rc;
-                    src2 = dst;
-                }
-                return WX_OK;
-            }
-        }
-    }
-    {
-        // leaves of a tree, dense (iwpt) or in the columns of a packet table (iwpd by tree: colmap is set, the leaves of depth
-        // l sit in column l): the lattice inverse takes them in level by level (wx_lattice_tree.h)
-        if (!force_generic && !noreg && status) {
-            const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, colmap ? n : 0, filt, status,
-                                              nstatus, st);
-            if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, colmap != nullptr, 0, 0, is != n);
-            if (r) return r < 0 ? r : WX_OK;
-        }
-        if (!force_generic && !noreg && !status && !colmap && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 &&
-            wx_lattice_tree_applicable_T<T>(n, filt)) {
-            const uint8_t *ones = wx_full_tree_ones(st);
-            if (ones) {
-                const int r = wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st);
-                if (r == 1) WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n);
-                if (r) return r < 0 ? r : WX_OK;
-            }
-        }
+    // leaves of a tree, dense (iwpt) or in the columns of a packet table (iwpd by tree: colmap is set, the leaves of depth
+    // l sit in column l): the lattice inverse takes them in level by level (wx_lattice_tree.h)
+    if (!force_generic && !noreg && status)
+        WX_ATTEMPT(wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, colmap ? n : 0, filt, status, nstatus, st),
+                   WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 0, colmap != nullptr, 0, 0, is != n));
+    // a full tree nothing above took, as a tree
+    if (reg_full && L <= 12 && (n >= 1024 || (n >= 64 && filt.F > 8)) && n <= 4096 && wx_lattice_tree_applicable_T<T>(n, filt)) {
+        const uint8_t *ones = wx_full_tree_ones(st);
+        if (ones)
+            WX_ATTEMPT(wx_lattice_tree_T<T>(true, xw, xh, n, L, batch, is, 0, filt, ones, ((int64_t)1 << L) - 1, st),
+                       WX_DWT1D_TRACE(WX_R1_LATTREE, 1, sizeof(T), n, L, L, batch, filt.F, 1, 0, 0, 0, is != n));
     }
     if (!force_generic && wx_fused1d_ok<T>(n, filt.F)) {
         WX_DWT1D_TRACE_DEPTH(L);
