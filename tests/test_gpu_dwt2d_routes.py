@@ -64,30 +64,27 @@ Routes (csrc/wx_debug.h) and the cases that pin them; NS = lattice stages = F / 
   COPYB     ahead of the two-pass levels of an inverse that ends in tile levels (tail-*, tile-*-rand, -deep, q64t-*-F18)
   GATHER    iwpd along a tree that is not full: q64w-*-tree, wpd-*-128-tree
 
-Not reachable from any public call (the condition is quoted from the code; none of these instances is deleted here):
-  * k_rows_fused<T, F, *, 1> (V = 1) for F <= 12: `vec` needs `m % VW == 0 && R % VW == 0 && S % VW == 0 && src_img % VW == 0 &&
-    dst_img % VW == 0` and 16-byte pointers.  wx_fused1d_ok (`!wx_is_pow2(n) || n < 8`) leaves m a power of two >= 8, so m and
-    the image strides m n, m n k are multiples of 8; wx_rows_geometry ends at `R > VW` / `(R + R / 4) % VW == 0`; WxIO::in /
-    ::out hand the kernels an "aligned device copy if p is a misaligned device pointer" (wx_host.h) and the scratch images come
-    from the allocator.  Only `filt.F <= 12` is left: V = 1 runs for 14 .. 20 taps and nowhere else.
-  * KI = 1, with and without REGL: `items_per_lane <= 1` means n R <= 2048 VW, `(size_t)n * S * sizeof(T) > 40 * 1024` means
-    n S > 2560 VW, and S <= R + R / 4: n R > 2048 VW.
-  * <VW, 0, true> (register levels without in place): `regl` needs `(sizeof(T) == 8 && n >= 256) || n >= 1024`; for every such n
-    the fast path takes (`(size_t)2 * n * S * sizeof(T) <= 160 * 1024`: up to 4096 columns) n S sizeof(T) is 64 or 80 KiB,
-    inside the in-place window `<= 80 * 1024 && > 40 * 1024`, with two items per lane.
-  * <VW, 2, false> in Float64: the in-place window starts at 256 columns of Float64, where `regl` always holds.
-  * KI > 0 or REGL above 8 taps: `filt.F <= 8` in both `inplace` and `regl`.
-  * LROWS in Float32: `return 0; // not built since round 6` (wx_lattice_rows.hip); LROWS at 1024 columns: `n == 512 ? 3 :
-    (n == 256 ? 4 : (n == 128 ? 5 : -1))`.
+Not reachable from any public call.  The template instances that earlier versions of this list named are no longer built; the
+proofs, with the conditions as they stood, are in profiles/dwt2d_routes.md ("Removed as unreachable"):
+  * k_rows_fused: V = 1 up to 12 taps and V = VW above (the launcher answers WX_EUNSUPPORTED for rows, strides or pointers off the
+    16-byte vectors: wx_fused1d_ok leaves m a power of two >= 8, wx_rows_geometry ends at `R > VW` / `(R + R / 4) % VW == 0`, WxIO
+    re-aligns device pointers, the scratch images come from the allocator), KI = 1, register levels without in place, in place
+    without register levels in Float64; KI > 0 or REGL above 8 taps was never instantiated (`filt.F <= 8` in `inplace`).
+  * k_dwt2d_level_tile_p above 10 taps and in Float32 at 10 taps (NBP = (80 * 80 + 255) / 256 = 25: `if constexpr (NBP <= 24 && F <=
+    10)`); k_idwt2d_level_tile_p in Float32 and above 8 taps (`if constexpr (NBP <= 24 && F <= 8 && sizeof(T) == 8)`).
+  * L2DC at 512 x 512 and 1024 x 1024, and in the inverse (k_lat2d_icolT_f32): only the diagnostic knob WX_L2D_FUSED, which is gone,
+    reached them; the fused launcher declines only `if constexpr (HB == 1)` forward instances, which take the 256 x 256 forward
+    pair (wx_lattice2d_launch_256), and `batch < per`, misaligned pointers and in-place odd batches, which the pair declines too.
   * k_lat2d64_wpd<3>: `wx_lat_stages_of(int ns) { return ns <= 2 ? ns : ((ns + 1) & ~1); }` never returns 3 (6 taps run NS = 4).
-  * TILEP with (by_node, status) = (0, 1): `NBP <= 24 && F <= 10 && (!tt.status || by_node)`; (1, 0) in TILE and TILEP:
-    `by_node = tt.status && tt.act && ...`.  TILEP in Float32 at 10 taps: NBP = (80 * 80 + 255) / 256 = 25, `NBP <= 24`.
-  * ITILEP in Float32 or above 8 taps: `NBP <= 24 && F <= 8 && sizeof(T) == 8 && by_node`; ITILE / ITILEP without a tree status:
-    `if (!wx_level_tile_ok<T>(m, n, d, filt.F) || !tt.status) return false;`.
-  * TWO with a tree status and no node list (0, *, 1): wx_api_2d.hip sets `htree` wherever it sets `dstatus`.
-  * L2DC at 512 x 512 and 1024 x 1024, and in the inverse: the fused launcher declines only `if constexpr (HB == 1)` forward
-    instances, `batch < per` and in-place odd batches, which wx_lattice2d_launch declines too; otherwise only the diagnostic
-    knob `wx_getenv("WX_L2D_FUSED")` reaches the pair.
+Still built though unreachable, because they are paths inside kernels that run (removing them would change those kernels):
+  * LROWS in Float32 is compiled out at the call (`if constexpr (sizeof(T) == 8)` in wx_launch_rows); LROWS at 1024 columns:
+    `n == 512 ? 3 : (n == 256 ? 4 : (n == 128 ? 5 : -1))`.
+  * TILEP with (by_node, status) = (0, 1), the whole-image walk under a tree status without a node list in the persistent kernels:
+    `if (!tt.status || by_node)`; (1, 0) in TILE and TILEP: `by_node = tt.status && tt.act && ...`.
+  * ITILE / ITILEP without a tree status: `if (!wx_level_tile_ok<T>(m, n, d, filt.F) || !tt.status) return false;`; ITILEP without a
+    node list: `if (by_node)`.
+  * TWO with a tree status and no node list (0, *, 1), the `status` branch of k_dwt2d_dim1 / _dim2 without `act`: wx_api_2d.hip sets
+    `htree` wherever it sets `dstatus`, and wx_dev_wpt2d answers WX_EUNSUPPORTED for a status without it.
 Reachable and not pinned here, each for its size: L2DF with more than one piece (a batch of more than 65534 units) and the
 host loop `for (int64_t b0 = 0; b0 < batch; b0 += 65535)` of TILE / ITILE (more than 65535 images of at least one tile: 2 GB).
 The persistent loop of L2DF, the ticket ring of its second pass, and batches beyond one ring are the subject of

@@ -6,10 +6,10 @@
 
 #include <stdlib.h>
 
-// Test hooks.  The library reads six WX_* environment variables -- WX_FWD_MODE, WX_LATTICE2D, WX_LATTICE2D_DEEP, WX_LATROWS_MINSH,
-// WX_SHRINK_WG_MAX, WX_L2D_FUSED: the A/B tests of tests/ and tools/dbg/fused2d_dbg.py, DESIGN.md section 10 -- and ONLY when the process
-// also sets WX_KNOBS=1: a production process's dispatch does not depend on its environment, and the header's statement about library
-// state holds.  Each is read once, at its first use.
+// Test hooks.  The library reads five WX_* environment variables -- WX_FWD_MODE, WX_LATTICE2D, WX_LATTICE2D_DEEP, WX_LATROWS_MINSH,
+// WX_SHRINK_WG_MAX: the A/B tests of tests/, DESIGN.md section 10 -- and ONLY when the process also sets WX_KNOBS=1: a production
+// process's dispatch does not depend on its environment, and the header's statement about library state holds.
+// Each is read once, at its first use.
 static inline const char *wx_getenv(const char *name)
 {
     static const bool on = [] { const char *k = getenv("WX_KNOBS"); return k && atoi(k) != 0; }();

@@ -88,7 +88,7 @@ int64_t wx_debug_swt1d_trace_dropped(void);
  *     6  TAIL      k_dwt2d_tail<T, F>: the K levels from the 8 x 8 approximation on   F, m   (depth is not known there: 0)
  *     7  L2DF      k_lat2d_fused_f32<NS, inverse, HB, E>: both passes, one piece     NS, HB, E, units of the piece
  *                  (a batch of more than 65534 units is as many consecutive L2DF rows as it has pieces)
- *     8  L2DC      k_lat2d_colT_f32 / _icolT_f32<NS, .., HB>: one transposing pass   NS, HB, pass (1 / 2)
+ *     8  L2DC      k_lat2d_colT_f32<NS, .., HB = 1>: one transposing pass, forward   NS, HB, pass (1 / 2)
  *     9  COL1D     the column pass of the fast path: ONE row from the 2-D caller for the call of the 1-D dispatch
  *                  (wx_dev_wpt1d / wx_dev_iwpt1d; its kernels appear in the 1-D record below when that one is armed, not
  *                  here); block, grid and LDS are 0                                  m, n

@@ -512,18 +512,21 @@ template <typename T, bool INVERSE>
 static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img, int64_t m, int64_t n, int L,
                           int64_t batch, const WxFilt &filt, hipStream_t st)
 {
-    // images of 128, 256, 512 columns: the rows of a wavefront as interleaved signals of the lattice kernels (wx_lattice_rows.h)
-    if (batch > 0) {
+    // Float64 images of 128, 256, 512 columns: the rows of a wavefront as interleaved signals of the lattice kernels (wx_lattice_rows.h)
+    if constexpr (sizeof(T) == 8) if (batch > 0) {
         const int r = wx_lattice_rows(INVERSE, src, dst, src_img, dst_img, m, n, L, batch, filt, st);
         if (r) return r < 0 ? r : WX_OK;
     }
     int R, S;
     wx_rows_geometry<T>(n, R, S);
     size_t lds = (size_t)2 * n * S * sizeof(T);
-    // 16-byte row vectors when the geometry and the pointers allow it
+    // 16-byte row vectors up to 12 taps (2F-tap window of vectors in registers), one row per lane above.  The vector kernels need
+    // the geometry and the pointers on 16 bytes, which every caller provides (profiles/dwt2d_routes.md): no scalar kernel is built for them
     constexpr int VW = 16 / (int)sizeof(T);
-    const bool vec = m % VW == 0 && R % VW == 0 && S % VW == 0 && src_img % VW == 0 && dst_img % VW == 0 &&
-                     ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0) && filt.F <= 12;     // 2F-tap window of vectors in registers
+    const bool vec = filt.F <= 12;
+    if (vec && !(m % VW == 0 && R % VW == 0 && S % VW == 0 && src_img % VW == 0 && dst_img % VW == 0 &&
+                 ((uintptr_t)src % 16 == 0) && ((uintptr_t)dst % 16 == 0)))
+        return wx_set_error(WX_EUNSUPPORTED, "fused row pass: rows, image strides or pointers off the 16-byte vectors");
     void (*kern)(const T *, T *, int64_t, int64_t, int, int, int, int64_t, WxFilt, int, int, int, int) = nullptr;
     int kV = 0, kKI = 0, kREGL = 0;                    // the template arguments of `kern`, set where it is chosen (launch record)
 #define WX_ROWS_PICK(FF, VV, KK, RR) (kV = VV, kKI = KK, kREGL = RR, k_rows_fused<T, FF, INVERSE, VV, KK, RR>)
@@ -541,22 +544,26 @@ static int wx_launch_rows(const T *src, T *dst, int64_t src_img, int64_t dst_img
     const int nt = inplace ? nt_ip : (per_cu >= 4 ? 256 : (per_cu >= 2 ? 512 : 1024));
     // measured (db4, full depth, 1 GiB): rows of 256 Float64 columns 1.11 -> 0.97 ms, 1024 Float32 columns 1.89 -> 1.65 ms; short rows lose
     // (64 Float32 columns 1.02 -> 1.34 ms, 64 / 128 Float64 columns 1.04 -> 1.39 ms)
-    const bool regl = vec && filt.F <= 8 && ((sizeof(T) == 8 && n >= 256) || n >= 1024);
+    // (every geometry of these widths is in place: the register levels come in the in-place form only, and the Float64 in-place window
+    // starts at 256 columns, so Float64 has no in-place kernel without them)
+    const bool regl = inplace && ((sizeof(T) == 8 && n >= 256) || n >= 1024);
     switch (filt.F) {
-#define WX_CASE(FF) case FF: kern = vec ? WX_ROWS_PICK(FF, VW, 0, false) : WX_ROWS_PICK(FF, 1, 0, false); break;
-        WX_CASE(10) WX_CASE(12) WX_CASE(14) WX_CASE(16) WX_CASE(18) WX_CASE(20)
-#undef WX_CASE
 #define WX_CASE(FF) case FF:                                                                                                                  \
-        if (regl) kern = inplace ? (items_per_lane <= 1 ? WX_ROWS_PICK(FF, VW, 1, true) : WX_ROWS_PICK(FF, VW, 2, true))                        \
-                                 : WX_ROWS_PICK(FF, VW, 0, true);                                                                             \
-        else kern = inplace ? (items_per_lane <= 1 ? WX_ROWS_PICK(FF, VW, 1, false) : WX_ROWS_PICK(FF, VW, 2, false))                        \
-                            : (vec ? WX_ROWS_PICK(FF, VW, 0, false) : WX_ROWS_PICK(FF, 1, 0, false));                                        \
+        if (regl) kern = WX_ROWS_PICK(FF, VW, 2, true);                                                                                       \
+        else if (!inplace) kern = WX_ROWS_PICK(FF, VW, 0, false);                                                                             \
+        else if constexpr (sizeof(T) == 4) kern = WX_ROWS_PICK(FF, VW, 2, false);                                                             \
         break;
         WX_CASE(2) WX_CASE(4) WX_CASE(6) WX_CASE(8)
 #undef WX_CASE
-    default: return wx_set_error(WX_EUNSUPPORTED, "no fused row kernel for this filter length");
+#define WX_CASE(FF) case FF: kern = WX_ROWS_PICK(FF, VW, 0, false); break;
+        WX_CASE(10) WX_CASE(12)
+#undef WX_CASE
+#define WX_CASE(FF) case FF: kern = WX_ROWS_PICK(FF, 1, 0, false); break;
+        WX_CASE(14) WX_CASE(16) WX_CASE(18) WX_CASE(20)
+#undef WX_CASE
     }
 #undef WX_ROWS_PICK
+    if (!kern) return wx_set_error(WX_EUNSUPPORTED, "no fused row kernel for this filter length and geometry");
     if (lds > 64 * 1024)
         WX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -592,33 +599,34 @@ int wx_dev_wpt2d_fast(const T *x, T *y, int64_t m, int64_t n, int L, int64_t bat
         // 512 x 512 Float32, depth 6: the transposing lattice kernel applied twice (wx_lattice2d.hip)
         if (wx_lattice2d_ok(m, n, L, filt, sizeof(T)) && in_img == mn) {
             // round 6: both passes in one persistent launch, the intermediate in a ring of <= 128 MiB of `tmp` that stays in the Infinity
-            // Cache (k_lat2d_fused_f32).  A launcher that declines (alignment, in-place odd batches of 256 x 256 images) leaves the two
-            // launches below.
-            if (wx_lattice2d_fused_on()) {                       // (`tmp` holds max(mn batch, wx_lattice2d_ring_elems) elements: wx_api_2d.hip)
-                WxScratch fscr(st);
-                unsigned *ctl = (unsigned *)fscr.alloc(wx_lattice2d_ctl_bytes());
-                if (!ctl) return WX_EHIP;
-                // a launch takes at most 65535 units (images, pairs of 256 x 256 images): longer batches in pieces, one after the other
-                const int64_t piece = 65534;
-                bool all = true;
-                for (int64_t b0 = 0; b0 < batch && all; b0 += piece) {
-                    const int64_t nb = batch - b0 < piece ? batch - b0 : piece;
-                    const int rf = wx_lattice2d_fused_f32((const float *)x + b0 * mn, (float *)y + b0 * mn, (float *)tmp, ctl, m, L, nb, filt, inverse, st);
-                    if (rf < 0) return rf;
-                    if (rf != 1) {
-                        if (b0) return wx_set_error(WX_EHIP, "lattice2d: the fused launch took a first piece of the batch and not the next");
-                        all = false;
-                    }
+            // Cache (k_lat2d_fused_f32).  (`tmp` holds max(mn batch, wx_lattice2d_ring_elems) elements: wx_api_2d.hip)
+            WxScratch fscr(st);
+            unsigned *ctl = (unsigned *)fscr.alloc(wx_lattice2d_ctl_bytes());
+            if (!ctl) return WX_EHIP;
+            // a launch takes at most 65535 units (images, pairs of 256 x 256 images): longer batches in pieces, one after the other
+            const int64_t piece = 65534;
+            bool all = true;
+            for (int64_t b0 = 0; b0 < batch && all; b0 += piece) {
+                const int64_t nb = batch - b0 < piece ? batch - b0 : piece;
+                const int rf = wx_lattice2d_fused_f32((const float *)x + b0 * mn, (float *)y + b0 * mn, (float *)tmp, ctl, m, L, nb, filt, inverse, st);
+                if (rf < 0) return rf;
+                if (rf != 1) {
+                    if (b0) return wx_set_error(WX_EHIP, "lattice2d: the fused launch took a first piece of the batch and not the next");
+                    all = false;
                 }
-                if (all) return WX_OK;
             }
-            // one launch per pass (what is still built of it: wx_lattice2d_launch), the whole batch through `tmp`
-            const int r1 = wx_lattice2d_colT_f32((const float *)x, (float *)tmp, m, L, batch, filt, inverse, 1, st);
-            if (r1 < 0) return r1;
-            if (r1 == 1) {
-                const int r2 = wx_lattice2d_colT_f32((const float *)tmp, (float *)y, m, L, batch, filt, inverse, 2, st);
-                if (r2 != 1) return r2 < 0 ? r2 : wx_set_error(WX_EHIP, "lattice2d: second pass not built for the first one's filter");
-                return WX_OK;
+            if (all) return WX_OK;
+            // What the fused launcher declines goes to the strips below (one image of 256 x 256, alignment, in-place odd batches of 256 x 256
+            // images), except the forward transform of 256 x 256 images deeper than the lattice's levels or at 18 / 20 taps, where its
+            // kernel spills: that one keeps the form of one launch per pass (wx_lattice2d_launch_256), the whole batch through `tmp`
+            if (!inverse) {
+                const int r1 = wx_lattice2d_colT_f32((const float *)x, (float *)tmp, m, L, batch, filt, 1, st);
+                if (r1 < 0) return r1;
+                if (r1 == 1) {
+                    const int r2 = wx_lattice2d_colT_f32((const float *)tmp, (float *)y, m, L, batch, filt, 2, st);
+                    if (r2 != 1) return r2 < 0 ? r2 : wx_set_error(WX_EHIP, "lattice2d: second pass not built for the first one's filter");
+                    return WX_OK;
+                }
             }
         }
     }
@@ -976,7 +984,8 @@ static bool wx_launch_level_tile_F(const T *src, T *dst, int64_t src_img, int64_
     T *di = (T *)tt.dst_int;
     // persistent workgroups with the next tile prefetched (k_dwt2d_level_tile_p): every tile does work (no tree, or the node list)
     constexpr int NBP = ((CR + 2 * H) * (CC + 2 * H) + 255) / 256;
-    if (NBP <= 24 && F <= 10 && (!tt.status || by_node)) {          // (longer filters spill at three wavefronts per SIMD)
+    // (longer filters spill at three wavefronts per SIMD: built for Float64 up to 10 taps and Float32 up to 8)
+    if constexpr (NBP <= 24 && F <= 10) if (!tt.status || by_node) {
         auto kp = k_dwt2d_level_tile_p<T, F, CR, CC>;
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1358,7 +1367,9 @@ static bool wx_launch_ilevel_tile_F(const T *src_leaf, int64_t leaf_img, const T
     const unsigned tiles = by_node ? (unsigned)(tt.nact * (mp / CR) * (np / CC)) : (unsigned)((m / CR) * (n / CC));
     if (tiles == 0) return true;
     constexpr int NBP = (4 * HRm * HCm + 255) / 256;
-    if (NBP <= 24 && F <= 8 && sizeof(T) == 8 && by_node) {          // (Float32: no gain, 1.32 vs 1.34 ms: instruction-bound)     // (Float32 at 8 taps spills 124 bytes per lane at three wavefronts per SIMD: 1.5 -> 1.8 ms)
+    // built for Float64 up to 8 taps (Float32: no gain, 1.32 vs 1.34 ms: instruction-bound; at 8 taps it spills 124 bytes per lane at
+    // three wavefronts per SIMD: 1.5 -> 1.8 ms)
+    if constexpr (NBP <= 24 && F <= 8 && sizeof(T) == 8) if (by_node) {
         auto kp = k_idwt2d_level_tile_p<T, F, CR, CC>;
         if (lds > 64 * 1024 &&
             hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -1480,39 +1491,31 @@ int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
         return WX_OK;
     }
     if (status) {
+        if (!htree) return wx_set_error(WX_EUNSUPPORTED, "2-D tree levels need the host copy of the tree");     // (wx_api_2d.hip passes both)
         // Tree-driven: a level rewrites exactly the blocks of the nodes it decomposes (children live where the
         // parent was), so all levels run in place on y through tmp and skip every other block -- the work is
         // proportional to the decomposed area (a dwt tree touches 1 + 1/4 + 1/16 + ... images, not L).
         // (block-row, block-column) of the decomposed nodes of every depth, from the host copy of the tree
         std::vector<const int *> dact((size_t)L, nullptr);
         std::vector<int> nact((size_t)L, 0);
-        if (htree) {
-            for (int d = 0; d < L; ++d) {
-                std::vector<int> lst;
-                int64_t start = 1;
-                for (int t = 0; t < d; ++t) start = 4 * start - 2;
-                const int64_t cnt = (int64_t)1 << (2 * d);
-                for (int64_t mo = 0; mo < cnt; ++mo) {
-                    const int64_t hp = start + mo;
-                    if (!(hp <= nstatus && htree[hp - 1])) continue;
-                    int jr = 0, jc = 0;
-                    for (int t = 0; t < d; ++t) { jr |= (int)((mo >> (2 * t + 1)) & 1) << t; jc |= (int)((mo >> (2 * t)) & 1) << t; }
-                    lst.push_back(jr); lst.push_back(jc);
-                }
-                nact[(size_t)d] = (int)(lst.size() / 2);
-                if (!lst.empty()) {
-                    dact[(size_t)d] = (const int *)wx_const_upload(lst.data(), lst.size() * sizeof(int), st, true);
-                    if (!dact[(size_t)d]) return WX_EHIP;
-                }
+        for (int d = 0; d < L; ++d) {
+            std::vector<int> lst;
+            int64_t start = 1;
+            for (int t = 0; t < d; ++t) start = 4 * start - 2;
+            const int64_t cnt = (int64_t)1 << (2 * d);
+            for (int64_t mo = 0; mo < cnt; ++mo) {
+                const int64_t hp = start + mo;
+                if (!(hp <= nstatus && htree[hp - 1])) continue;
+                int jr = 0, jc = 0;
+                for (int t = 0; t < d; ++t) { jr |= (int)((mo >> (2 * t + 1)) & 1) << t; jc |= (int)((mo >> (2 * t)) & 1) << t; }
+                lst.push_back(jr); lst.push_back(jc);
+            }
+            nact[(size_t)d] = (int)(lst.size() / 2);
+            if (!lst.empty()) {
+                dact[(size_t)d] = (const int *)wx_const_upload(lst.data(), lst.size() * sizeof(int), st, true);
+                if (!dact[(size_t)d]) return WX_EHIP;
             }
         }
-        auto level = [&](const T *src, int64_t simg, int d, bool inv, int copy) {
-            if (htree && nact[(size_t)d] == 0) return;                     // nothing decomposed at this depth
-            if (inv) wx_launch_level2d<T, true>(src, tmp, y, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, copy,
-                                                htree ? dact[(size_t)d] : nullptr, nact[(size_t)d]);
-            else wx_launch_level2d<T, false>(src, tmp, y, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, copy,
-                                             htree ? dact[(size_t)d] : nullptr, nact[(size_t)d]);
-        };
         // levels whose nodes are at least 8 x 8 run as one tile pass each; a tree that goes deeper (a pyramid of full depth ends at
         // 1 x 1) continues on the small nodes with the two-pass level, block by block: until round 4 such a tree took the two-pass
         // level for EVERY level, the root's included -- four trips of the whole image (2-D idwtall: 8 % of the HBM peak)
@@ -1523,14 +1526,14 @@ int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
                (((m >> Lt) >= WX_TILE_CR && (n >> Lt) >= wx_tile_cc<T>()) ||
                 2 * (int64_t)nact[(size_t)Lt] * (m >> Lt) * (n >> Lt) >= mn))
             ++Lt;
-        auto level2 = [&](const T *src, int64_t simg, T *dstb, T *interm, int d, bool inv) {
-            if (nact[(size_t)d] == 0) return;
-            if (inv) wx_launch_level2d<T, true>(src, interm, dstb, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, 0,
+        auto level2 = [&](const T *src, int64_t simg, T *dstb, T *interm, int d, bool inv, int copy = 0) {
+            if (nact[(size_t)d] == 0) return;                              // nothing decomposed at this depth
+            if (inv) wx_launch_level2d<T, true>(src, interm, dstb, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, copy,
                                                 dact[(size_t)d], nact[(size_t)d]);
-            else wx_launch_level2d<T, false>(src, interm, dstb, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, 0,
+            else wx_launch_level2d<T, false>(src, interm, dstb, simg, mn, (int)m, (int)n, d, batch, filt, status, nstatus, st, copy,
                                              dact[(size_t)d], nact[(size_t)d]);
         };
-        if (!inverse && htree && (L == 1 || pong) && Lt >= 1) {
+        if (!inverse && (L == 1 || pong) && Lt >= 1) {
             // one pass per level: a level reads its nodes from the scratch image of its parity (the root from x),
             // sends the children that are decomposed further to the other scratch image and the leaves to y
             T *sc[2] = {tmp, pong};
@@ -1550,7 +1553,7 @@ int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
             WX_HIP_CHECK(hipGetLastError());
             return WX_OK;
         }
-        if (inverse && htree && (L == 1 || pong) && Lt >= 1) {
+        if (inverse && (L == 1 || pong) && Lt >= 1) {
             // the mirror image: a level takes the children that were rebuilt one level earlier from the scratch
             // image of their parity and the leaves from x, and writes the parents into the other scratch image (the
             // root into y)
@@ -1578,12 +1581,12 @@ int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
             return WX_OK;
         }
         if (!inverse) {
-            level(x, in_img, 0, false, 1);                                 // the root: every block is written
-            for (int d = 1; d < L; ++d) level(y, mn, d, false, 0);
+            level2(x, in_img, y, tmp, 0, false, 1);                        // the root: every block is written
+            for (int d = 1; d < L; ++d) level2(y, mn, y, tmp, d, false);
         } else {
             WX_HIP_CHECK(hipMemcpy2DAsync(y, mn * sizeof(T), x, in_img * sizeof(T), mn * sizeof(T), batch,
                                           hipMemcpyDeviceToDevice, st));
-            for (int d = L - 1; d >= 0; --d) level(y, mn, d, true, 0);
+            for (int d = L - 1; d >= 0; --d) level2(y, mn, y, tmp, d, true);
         }
         WX_HIP_CHECK(hipGetLastError());
         return WX_OK;

@@ -109,7 +109,7 @@ int wx_dev_wpd2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, c
 template <typename T>
 int wx_dev_wpt2d(const T *x, T *y, int64_t m, int64_t n, int L, int64_t batch, const WxFilt &filt,
                  const uint8_t *status, int64_t nstatus, T *tmp, T *pong, bool inverse, int64_t in_img,
-                 hipStream_t st, const uint8_t *htree = nullptr);
+                 hipStream_t st, const uint8_t *htree);                 // htree: the host copy of `status`, given whenever it is
 template <typename T>
 int wx_dev_gather_leaves2d(const T *Xw, T *out, int64_t m, int64_t n, int k, int64_t batch, const int *colmap,
                            int nblk, hipStream_t st);
@@ -173,20 +173,19 @@ int wx_lattice_tree8k_inv_f64(const double *x, double *y, int64_t batch, const W
 int wx_lattice_iwpt_f64(const double *xw, double *y, int64_t n, int L, int64_t batch, int64_t in_stride,
                         const WxFilt &filt, hipStream_t st);
 
-// 512 x 512 Float32 images, depth 6: one transposing lattice pass (wx_lattice2d.hip); 0 = not applicable, 1 = launched
+// 512 x 512 Float32 images, depth 6 (256 x 256: 5, 1024 x 1024: 7) on the transposing lattice kernel (wx_lattice2d.hip)
 bool wx_lattice2d_ok(int64_t m, int64_t n, int L, const WxFilt &filt, size_t esz);
-int wx_lattice2d_colT_f32(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, bool inverse, int pass, hipStream_t st);
+// one transposing pass per launch, forward, 256 x 256 images only (what the fused launch below declines there); pass 1 / 2 = first /
+// second pass of a transform; 0 = not applicable, 1 = launched, < 0 = error
+int wx_lattice2d_colT_f32(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, int pass, hipStream_t st);
 // both passes in one persistent launch through a cache-resident ring (round 6): 0 = not applicable, 1 = launched, < 0 = error
 int wx_lattice2d_fused_f32(const float *src, float *dst, float *ring, unsigned *ctl, int64_t m, int L, int64_t batch, const WxFilt &filt, bool inverse,
                            hipStream_t st);
 int64_t wx_lattice2d_ring_elems(int64_t m, int64_t batch);
 size_t wx_lattice2d_ctl_bytes();
-bool wx_lattice2d_fused_on();
 // row pass of a 2-D full tree on the lattice kernels (wx_lattice_rows.h, dispatch in wx_lattice_rows.hip): L levels along the rows of
-// (m, n) images; 0 = not applicable, 1 = launched, < 0 = error
+// (m, n) images; 0 = not applicable, 1 = launched, < 0 = error.  Float64 only: not built for Float32 since round 6
 int wx_lattice_rows(bool inverse, const double *x, double *y, int64_t in_img, int64_t out_img, int64_t m, int64_t n, int L, int64_t batch,
-                    const WxFilt &filt, hipStream_t st);
-int wx_lattice_rows(bool inverse, const float *x, float *y, int64_t in_img, int64_t out_img, int64_t m, int64_t n, int L, int64_t batch,
                     const WxFilt &filt, hipStream_t st);
 // 64 x 64 images, full quad tree of depth 1 .. 6 in ONE pass, an image per wavefront (wx_lattice_2d64.h); 0 = not applicable, 1 = launched.
 // in_img: elements between the images of the inverse's input (a slice of a packet table)

@@ -794,7 +794,7 @@ __device__ __forceinline__ void l2_inv_body(const float *__restrict__ simg, floa
     });
 }
 
-// one launch per pass: grid (column blocks, units)
+// one launch per pass: grid (column blocks, units).  Forward only, and launched for 256 x 256 images only (wx_lattice2d_256.hip)
 template <int NS, bool BL, bool BS, int HB>
 __global__ __launch_bounds__(64 * WX_L2D_W) __attribute__((amdgpu_waves_per_eu(WX_L2D_WPE, WX_L2D_WPE))) void k_lat2d_colT_f32(
     const float *__restrict__ src, float *__restrict__ dst, int last_img, WxLat2 cf, WxL2M mm)
@@ -805,16 +805,6 @@ __global__ __launch_bounds__(64 * WX_L2D_W) __attribute__((amdgpu_waves_per_eu(W
     // HB = 1: a workgroup takes two consecutive images; the last workgroup of an odd batch re-does the last two
     const int64_t img0 = min((int)blockIdx.y << G::IB, last_img);
     l2_fwd_body<NS, BL, BS, HB, 0>(src + img0 * G::IMG, dst + img0 * G::IMG, blockIdx.x, cf, mm, ldsb, threadIdx.x);
-}
-template <int NS, bool BL, bool BS, int HB>
-__global__ __launch_bounds__(64 * WX_L2D_W) __attribute__((amdgpu_waves_per_eu(WX_L2D_WPE, WX_L2D_WPE))) void k_lat2d_icolT_f32(
-    const float *__restrict__ src, float *__restrict__ dst, int last_img, WxLat2 cf, WxL2M mm)
-{
-    typedef L2G<HB> G;
-    __shared__ double lds[HB == 2 ? (256 * 18 > WX_L2D_W * WX_L2_WIN ? 256 * 18 : WX_L2D_W * WX_L2_WIN) : WX_L2D_W * WX_L2_WIN];
-    const unsigned ldsb = (unsigned)(uintptr_t)(double __attribute__((address_space(3))) *)lds;
-    const int64_t img0 = min((int)blockIdx.y << G::IB, last_img);
-    l2_inv_body<NS, BL, BS, HB, 0>(src + img0 * G::IMG, dst + img0 * G::IMG, blockIdx.x, cf, mm, ldsb, threadIdx.x);
 }
 
 // ---- both passes in ONE persistent launch, the intermediate image in a ring that stays in the Infinity Cache (round 6) -----------------
@@ -1072,50 +1062,5 @@ static int wx_lattice2d_fused_launch(const float *src, float *dst, float *ring, 
     WX_DWT2D_TRACE(WX_R2_L2DF, inverse, inverse ? L : 0, L, sizeof(float), grid, wg, 0, wx_lat_stages(filt.F), HB, hc.mm.e ? 1 : 0, fz.units);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return wx_set_hip_error(e, "lattice2d fused launch", __FILE__, __LINE__);
-    return 1;
-}
-
-// launch of one transposing pass for geometry HB (0: 512 x 512, 1: 256 x 256, 2: 1024 x 1024): one translation unit per geometry
-// (wx_lattice2d.hip, wx_lattice2d_256.hip, wx_lattice2d_1024.hip) so that the 60 kernels of each compile in parallel
-template <int HB>
-static int wx_lattice2d_launch(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, bool inverse, int pass, hipStream_t st)
-{
-    WxLat2 cf;
-    WxL2M mm;
-    if (!l2_prepare<HB>(filt, L, inverse, cf, mm)) return 0;
-    const int64_t per = HB == 1 ? 2 : 1, units = (batch + per - 1) / per;
-    if (batch < per || units > 65535 || ((uintptr_t)src & 15) || ((uintptr_t)dst & 15)) return 0;
-    if ((batch & (per - 1)) && src == dst) return 0;          // the last workgroup re-does images: out of place only
-    // Since round 6 a transform is ONE launch of k_lat2d_fused_f32; what is still built of the one-launch-per-pass form: the blocked pair
-    // for the forward transform of 256 x 256 images (at full depth its fused kernel spills: the launcher above declines), and the pair of
-    // db4 in every geometry and direction so that the fused launch can be timed against it on any box (WX_L2D_FUSED=0).  Anything else:
-    // 0 = not ours, the caller takes the strip kernels.  (The unblocked variant -- pass 0 -- is gone.)
-    if (WX_L2D_W != 4 || (pass != 1 && pass != 2)) return 0;
-    const bool bl = pass == 2;
-    const int nsq = wx_lat_stages(filt.F);
-    if (!((HB == 1 && !inverse) || nsq == 4)) return 0;
-    const int cols_wg = (HB == 2 ? 8 : 16) * WX_L2D_W;
-    const dim3 grid((unsigned)(m / cols_wg), (unsigned)units), wg(64 * WX_L2D_W);
-    const int last_img = (int)(batch - per);
-#define WX_GO2K(K, NSS)                                                                                                  \
-    do {                                                                                                                 \
-        if (bl) hipLaunchKernelGGL((K<NSS, true, false, HB>), grid, wg, 0, st, src, dst, last_img, cf, mm);                  \
-        else hipLaunchKernelGGL((K<NSS, false, true, HB>), grid, wg, 0, st, src, dst, last_img, cf, mm);                     \
-    } while (0)
-#define WX_GO2(NSS)                                                                                                      \
-    case NSS:                                                                                                            \
-        if (inverse) {                                                                                                   \
-            if constexpr (NSS == 4) WX_GO2K(k_lat2d_icolT_f32, NSS);                                                     \
-        } else if constexpr (HB == 1 || NSS == 4) WX_GO2K(k_lat2d_colT_f32, NSS);                                        \
-        break;
-    switch (nsq) {
-        WX_GO2(1) WX_GO2(2) WX_GO2(4) WX_GO2(6) WX_GO2(8) WX_GO2(10)
-    default: return 0;
-    }
-#undef WX_GO2
-#undef WX_GO2K
-    WX_DWT2D_TRACE(WX_R2_L2DC, inverse, inverse ? L : 0, L, sizeof(float), grid, wg, 0, nsq, HB, pass);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return wx_set_hip_error(e, "lattice2d launch", __FILE__, __LINE__);
     return 1;
 }

@@ -2,8 +2,7 @@
 // the kernels of the 512 x 512 geometry (depth 6).  Reference: 2-D wpt / iwpt by level, DWT.jl:500-548, 662-710.
 #include "wx_lattice2d.h"
 
-int wx_lattice2d_launch_256(const float *, float *, int64_t, int, int64_t, const WxFilt &, bool, int, hipStream_t);    // wx_lattice2d_256.hip
-int wx_lattice2d_launch_1024(const float *, float *, int64_t, int, int64_t, const WxFilt &, bool, int, hipStream_t);   // wx_lattice2d_1024.hip
+int wx_lattice2d_launch_256(const float *, float *, int64_t, int, int64_t, const WxFilt &, int, hipStream_t);         // wx_lattice2d_256.hip
 
 int wx_lattice2d_fused_256(const float *, float *, float *, unsigned *, int64_t, int, int64_t, const WxFilt &, bool, hipStream_t);
 int wx_lattice2d_fused_1024(const float *, float *, float *, unsigned *, int64_t, int, int64_t, const WxFilt &, bool, hipStream_t);
@@ -23,16 +22,11 @@ bool wx_lattice2d_ok(int64_t m, int64_t n, int L, const WxFilt &filt, size_t esz
     return !off && esz == 4 && shape && filt.F >= 2 && (filt.F & 1) == 0 && filt.F / 2 <= WX_L2_MAXS;
 }
 
-// one transposing pass over `batch` images of side `m` (512: depth 6, 256: depth 5, 1024: depth 7): 0 = not applicable,
-// 1 = launched, < 0 = error.  pass 0: natural image in, transposed image out (what one application of the kernel is);
-// pass 1 / 2: the first / second pass of a transform, with the intermediate image in the blocked layout of wx_lattice2d.h (the
-// caller's scratch buffer, never seen outside the library).
-int wx_lattice2d_colT_f32(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, bool inverse, int pass, hipStream_t st)
+// one transposing forward pass over `batch` images of side `m` in a launch of its own: built for 256 x 256 images only, where the
+// fused launch below declines deep trees and 18 / 20 taps.  0 = not applicable, 1 = launched, < 0 = error
+int wx_lattice2d_colT_f32(const float *src, float *dst, int64_t m, int L, int64_t batch, const WxFilt &filt, int pass, hipStream_t st)
 {
-    if (m == 512) return wx_lattice2d_launch<0>(src, dst, m, L, batch, filt, inverse, pass, st);
-    if (m == 256) return wx_lattice2d_launch_256(src, dst, m, L, batch, filt, inverse, pass, st);
-    if (m == 1024) return wx_lattice2d_launch_1024(src, dst, m, L, batch, filt, inverse, pass, st);
-    return 0;
+    return m == 256 ? wx_lattice2d_launch_256(src, dst, m, L, batch, filt, pass, st) : 0;
 }
 
 // both passes of a transform in one persistent launch, the intermediate image in a ring of wx_lattice2d_ring_elems(m, batch) elements that
@@ -54,8 +48,3 @@ int64_t wx_lattice2d_ring_elems(int64_t m, int64_t batch)
     return 0;
 }
 size_t wx_lattice2d_ctl_bytes() { return WX_L2F_CTL_BYTES; }
-bool wx_lattice2d_fused_on()
-{
-    static const bool off = wx_getenv("WX_L2D_FUSED") && atoi(wx_getenv("WX_L2D_FUSED")) == 0;
-    return !off;
-}

@@ -34,7 +34,3 @@ int wx_lattice_rows(bool inverse, const double *x, double *y, int64_t in_img, in
     if (SH == 4) return inverse ? wx_lattice_rows_4i_f64(x, y, in_img, out_img, m, L, batch, filt, st) : wx_lattice_rows_4f_f64(x, y, in_img, out_img, m, L, batch, filt, st);
     return inverse ? wx_lattice_rows_5i_f64(x, y, in_img, out_img, m, L, batch, filt, st) : wx_lattice_rows_5f_f64(x, y, in_img, out_img, m, L, batch, filt, st);
 }
-int wx_lattice_rows(bool, const float *, float *, int64_t, int64_t, int64_t, int64_t, int, int64_t, const WxFilt &, hipStream_t)
-{
-    return 0;                                                 // not built since round 6 (see above): the LDS strips
-}
