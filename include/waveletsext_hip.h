@@ -382,6 +382,40 @@ int wx_iswpd1d_trees_f32(const float *xw, float *x, int64_t n, int64_t ncols, co
 int wx_iacwpd1d_trees_f64(const double *xw, double *x, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch,
                           void *stream);
 
+/* denoise / denoiseall(xw, :swpd | :acwpd, wt; tree, dnt, estnoise, smooth) with ONE tree per signal: signal b is denoised from its
+ * redundant packet table xw[:, :, b] (heap ordered, node i in column i - 1) in the basis of column b of `trees`.  The reference takes a
+ * single BitVector (Denoising.jl:544-594); this is its loop with the (ntree, batch) convention of getbasiscoefall (Utils.jl:199-225), as
+ * wx_denoise_wpt1d_trees_* and wx_iswpd1d_trees_*.  For signal b with tree T_b:
+ *   sigma_b = noisest(xw[:, :, b], true, T_b) (Denoising.jl:228-231) = mad of the whole column of the finest detail node of T_b (from the
+ *             root by right children while i <= ntree && T_b[i], Utils.jl:428-433) / 0.6745, with the arithmetic and the non-finite rules
+ *             of wx_noisest_* (bit for bit);
+ *   the leaf columns of T_b (getleaf(tree, :binary), Denoising.jl:550-558, 583-591) pass threshold(v, th_kind, (T)(sigma_b * scale)), the
+ *             rounding of wx_threshold_*; with undersmooth != 0 the coarsest scaling node (from the root by left children while
+ *             i < ntree && T_b[i], Utils.jl:363-367) is left alone;
+ *   out[:, b] = iswpd(x~, wt, T_b), average based (Denoising.jl:561 passes no shift), or iacwpd(x~, T_b) (Denoising.jl:594).
+ * xw: (n, ncols, batch), never modified; out == xw returns WX_EARG.  out: (n, batch); for wx_denoise_swpd1d_trees_* with qmf == NULL
+ * (wt = nothing) out is (n, ncols, batch) and receives x~, the table with the leaf columns thresholded and every other column copied.
+ * out == NULL: only sigma is computed.  thr != NULL (nthr = 1 or batch values, host or device): the thresholds before scaling, and
+ * nothing is estimated.  sigma (optional, host or device, batch values): the estimates, or the thresholds used before scaling.
+ * trees: host or device, checked and packed exactly as for wx_iswpd1d_trees_* (the lowest offending column decides; a rejected call has
+ * written nothing).  Routes: inside the window -- n dyadic, 8 <= n <= 1024, even filters of 2 .. 20 taps, 2 D n sizeof(T) + the tree bits +
+ * 528 bytes <= 136 KiB with D the deepest tree the table holds -- one launch (csrc/wx_denoise_red_trees.hip: the estimate by one
+ * wavefront, then the depth-first walk of wx_red_trees.hip with the threshold on its leaf loads; no scratch memory); the table copy of
+ * wt = nothing is an estimate launch and an elementwise launch.  Byte-identical columns go to wx_noisest_*, wx_threshold_* with the leaf
+ * mask and wx_iswpd1d_* / wx_iacwpd1d_f64 whole; outside the window those run once per signal: correct and slow.
+ * wx_wpt_trees_last_route reports the route.
+ * Before a device is needed: bad dimensions, NULL trees, th_kind outside 0 .. 3, nthr not 0, 1 or batch (0 exactly when thr == NULL),
+ * neither out nor sigma: WX_EARG; n not dyadic, ntree != n - 1, an invalid column: WX_EASSERT; a column deeper than the table
+ * (2^(depth + 1) - 1 > ncols): WX_EBOUNDS.  batch == 0 is WX_OK. */
+int wx_denoise_swpd1d_trees_f64(const double *xw, double *out, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                const double *qmf, int F, int th_kind, double scale, const double *thr, int64_t nthr, int undersmooth,
+                                double *sigma, void *stream);
+int wx_denoise_swpd1d_trees_f32(const float *xw, float *out, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                const double *qmf, int F, int th_kind, double scale, const float *thr, int64_t nthr, int undersmooth,
+                                float *sigma, void *stream);
+int wx_denoise_acwpd1d_trees_f64(const double *xw, double *out, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                 int th_kind, double scale, const double *thr, int64_t nthr, int undersmooth, double *sigma, void *stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Standard (per-signal) best basis, BB -- SURVEY 8(f) row 3, widened after the 8(a) rows.

@@ -141,6 +141,8 @@ _EXTRA_SIGS = {
     "wx_denoise_wpt1d_trees": [_P, _P, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
     "wx_iswpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _L, _P, _I, _P],
     "wx_iacwpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _P],
+    "wx_denoise_swpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
+    "wx_denoise_acwpd1d_trees": [_P, _P, _L, _L, _P, _L, _L, _I, ctypes.c_double, _P, _L, _I, _P, _P],
     "wx_jbb_moments": [_P, _P, _P, _L, _L, _I, _P],
     "wx_jbb_costs": [_P, _P, _L, _L, _L, _I, _I, ctypes.c_double, _P, _P],
     "wx_acwpd_jbb_moments": [_P, _P, _P, _L, _I, _L, _P, _I, _I, _P],

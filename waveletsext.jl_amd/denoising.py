@@ -211,33 +211,58 @@ def _is_tree_matrix(tree):
     return tree is not None and np.ndim(tree) == 2
 
 
-def _trees_call(xa, N, wt, trees, th_kind, scale, thr, smooth, want_out, want_sigma):
-    """wx_denoise_wpt1d_trees_*: (xhat | None, sigma | None) as Args of the input's kind; thr: None (the noise is estimated per signal, each
-    on the finest detail node of its own tree) or 1 / N host values, the thresholds before scaling"""
+def _trees_call(xa, N, wt, trees, th_kind, scale, thr, smooth, want_out, want_sigma, inputtype="wpt"):
+    """wx_denoise_wpt1d_trees_* / wx_denoise_swpd1d_trees_* / wx_denoise_acwpd1d_trees_f64: (xhat | None, sigma | None) as Args of the input's
+    kind; thr: None (the noise is estimated per signal, each on the finest detail node of its own tree) or 1 / N host values, the thresholds
+    before scaling.  A redundant table (n, ncols, N) gives (n, N) signals, or with :swpd and wt = None the thresholded table"""
     from ._arrays import qmf_arg, trees_arg
     null = ctypes.c_void_p(0)
     q, qp, F = (None, null, 0) if wt is None else qmf_arg(wt)
     tb, tp, nt = trees_arg(trees, N, xa)
-    out = xa.new(xa.shape) if want_out else None
+    n = xa.shape[0]
+    if inputtype == "wpt" or (inputtype == "swpd" and wt is None):
+        oshape = tuple(xa.shape)
+    else:
+        oshape = (n,) + tuple(xa.shape[2:])                            # (n, ncols[, N]) -> (n[, N])
+    out = xa.new(oshape) if want_out else None
     sig = xa.new((N,)) if want_sigma else None
     tv = None if thr is None else np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=xa.dtype)))
-    fn = getattr(_lib.lib(), "wx_denoise_wpt1d_trees" + xa.suffix)
-    _lib.check(fn(xa.ptr, out.ptr if want_out else null, xa.shape[0], tp, nt, N, qp, F, int(th_kind), float(scale),
-                  null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
-                  1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream()))
+    tail = (int(th_kind), float(scale), null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
+            1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream())
+    optr = out.ptr if want_out else null
+    if inputtype == "wpt":
+        fn = getattr(_lib.lib(), "wx_denoise_wpt1d_trees" + xa.suffix)
+        _lib.check(fn(xa.ptr, optr, n, tp, nt, N, qp, F, *tail))
+    elif inputtype == "swpd":
+        fn = getattr(_lib.lib(), "wx_denoise_swpd1d_trees" + xa.suffix)
+        _lib.check(fn(xa.ptr, optr, n, xa.shape[1], tp, nt, N, qp, F, *tail))
+    else:
+        if xa.suffix != "_f64":
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "the autocorrelation transforms are Float64 only")
+        _lib.check(_lib.lib().wx_denoise_acwpd1d_trees_f64(xa.ptr, optr, n, xa.shape[1], tp, nt, N, *tail))
     return out, sig
 
 
+# a packet table in host memory keeps the refusal it always had: the table is (2^(D+1) - 1) times the signals, its upload would be the
+# call; the C entries take either
+_RED_HOST = "a tree matrix (one tree per signal) on a redundant packet table needs the table on the device (host arrays: inputtype = :wpt)"
+
+
 def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batched):
-    """denoise / denoiseall(x, :wpt, wt; tree = M) with M an (n - 1, N) matrix: signal i in the basis of column i (csrc/wx_denoise_trees.hip)"""
-    if inputtype != "wpt":
-        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs inputtype = :wpt")
-    if xa.arr.ndim != (2 if batched else 1):
+    """denoise / denoiseall(x, :wpt | :swpd | :acwpd, wt; tree = M) with M an (n - 1, N) matrix: signal i in the basis of column i
+    (csrc/wx_denoise_trees.hip; from a redundant packet table, a device tensor, csrc/wx_denoise_red_trees.hip)"""
+    if inputtype not in ("wpt", "swpd", "acwpd"):
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs inputtype = :wpt, :swpd or :acwpd")
+    red = inputtype != "wpt"
+    if xa.arr.ndim != (2 if batched else 1) + (1 if red else 0):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals")
     N = xa.shape[-1] if batched else 1
     if estnoise is None or estnoise is noisest:
         thr = None
     elif estnoise is relerrorthreshold or estnoise is surethreshold:
+        if red:
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant table: the selections "
+                                                     "have no per-signal leaf masks")
         # all coefficients of a non-redundant signal, whatever its tree (Denoising.jl:150-157, 293-300)
         thr = _select(xa, batched, False, None, 1 if estnoise is relerrorthreshold else 0)
     elif callable(estnoise):
@@ -245,21 +270,27 @@ def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batc
                            "noise estimates on the device path: noisest, relerrorthreshold, surethreshold or precomputed values")
     else:
         thr = np.broadcast_to(np.asarray(estnoise, dtype=np.float64), (N,)).astype(xa.dtype)
+    if red and xa.kind != "torch":
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, _RED_HOST)
     if bestTH is not None:                                             # one summary threshold for the batch, Denoising.jl:697-700
         if thr is None:
-            thr = to_numpy(_trees_call(xa, N, None, trees, dnt.th.kind, dnt.t, None, smooth, False, True)[1].arr)
+            thr = to_numpy(_trees_call(xa, N, None, trees, dnt.th.kind, dnt.t, None, smooth, False, True, inputtype)[1].arr)
         thr = np.full(1, bestTH(np.asarray(thr, dtype=np.float64)), dtype=xa.dtype)
-    return _trees_call(xa, N, wt, trees, dnt.th.kind, dnt.t, thr, smooth, True, False)[0].arr
+    return _trees_call(xa, N, wt, trees, dnt.th.kind, dnt.t, thr, smooth, True, False, inputtype)[0].arr
 
 
 def noisestall(x, redundant=False, tree=None):
     """noisest (Denoising.jl:214-232) of every signal of a batch (last axis): `tree` is None, one tree for all, or an (n - 1, N) matrix with
-    the tree of signal i in column i (then each estimate comes from the finest detail node of its own tree)"""
+    the tree of signal i in column i (then each estimate comes from the finest detail node of its own tree; redundant: x is the
+    (n, ncols, N) packet table of swpdall / acwpdall, a device tensor)"""
     xa = Arg(x)
     if _is_tree_matrix(tree):
-        if redundant or xa.arr.ndim != 2:
-            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs non-redundant 1-D signals")
-        return _trees_call(xa, xa.shape[-1], None, tree, 0, 1.0, None, "regular", False, True)[1].arr
+        if xa.arr.ndim != (3 if redundant else 2):
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals")
+        if redundant and xa.kind != "torch":
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, _RED_HOST)
+        # a redundant table: the column of the finest detail node, whichever transform filled it (the :swpd entry needs no filter for this)
+        return _trees_call(xa, xa.shape[-1], None, tree, 0, 1.0, None, "regular", False, True, "swpd" if redundant else "wpt")[1].arr
     it = ("sdwt" if tree is None else "swpd") if redundant else ("dwt" if tree is None else "wpt")
     sig = _noisest(xa, True, it, None if tree is None else np.asarray(tree, dtype=bool), on_device=xa.kind == "torch")
     return sig.arr if isinstance(sig, Arg) else sig

@@ -878,6 +878,36 @@ function noisestall(xw::HIP{T,2}, redundant::Bool, trees::BitMatrix) where T<:FT
     check(wx_denoise_wpt1d_trees(T, raw(xw), C_NULL, n, tb, size(tb, 1), N, C_NULL, 0, 0, 1.0, C_NULL, 0, 0, sigma, stream()))
     return sigma
 end
+"iswpdall / iacwpdall(x̃, ...) of the table with the leaf columns of every signal's own tree thresholded by σᵢ t (column i of `trees` for
+signal i), σᵢ = noisest(xwᵢ, true, treeᵢ) or σ = thr (one value, or one per signal): one launch (wx_denoise_swpd1d_trees_* /
+wx_denoise_acwpd1d_trees_f64); inputtype :swpd with wt = nothing returns x̃, the thresholded table"
+function denoiseall_red_trees(xw::HIP{T,3}, inputtype::Symbol, wt::Union{OrthoFilter,Nothing}, trees::BitMatrix, th::THType, t::Real,
+                              undersmooth::Bool; thr::Union{Vector{T},Nothing} = nothing) where T<:FT
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    tb = Matrix{UInt8}(trees)
+    tv = thr === nothing ? C_NULL : thr; ntv = thr === nothing ? 0 : length(thr)
+    if inputtype === :acwpd
+        x̂ = newlike(xw, T, (n, N))
+        check(wx_denoise_acwpd1d_trees(Float64, raw(xw), x̂, n, k, tb, size(tb, 1), N, thkind(th), Float64(t), tv, ntv, undersmooth ? 1 : 0,
+                                       C_NULL, stream()))
+        return x̂
+    end
+    x̂ = newlike(xw, T, wt === nothing ? (n, k, N) : (n, N))
+    q = wt === nothing ? C_NULL : qmfvec(wt)
+    check(wx_denoise_swpd1d_trees(T, raw(xw), x̂, n, k, tb, size(tb, 1), N, q, wt === nothing ? 0 : length(q), thkind(th), Float64(t), tv, ntv,
+                                  undersmooth ? 1 : 0, C_NULL, stream()))
+    return x̂
+end
+"noisest of every signal on the column of the finest detail node of its own tree (column i of `trees`) of a redundant packet table"
+function noisestall(xw::HIP{T,3}, redundant::Bool, trees::BitMatrix) where T<:FT
+    redundant || throw(ArgumentError("a table (n, ncols, N) with a tree matrix is a redundant packet table"))
+    n, k, N = size(xw)
+    @assert size(trees, 2) == N
+    sigma = Vector{T}(undef, N); tb = Matrix{UInt8}(trees)
+    check(wx_denoise_swpd1d_trees(T, raw(xw), C_NULL, n, k, tb, size(tb, 1), N, C_NULL, 0, 0, 1.0, C_NULL, 0, 0, sigma, stream()))
+    return sigma
+end
 # surethreshold / relerrorthreshold of one signal (Denoising.jl:146-166, 285-327) and of every signal of a batch (what
 # SureShrink(xw, redundant, tree) and denoiseall(...; estnoise = relerrorthreshold) evaluate signal by signal)
 function surethresholdall(coef::HIP{T}, redundant::Bool, tree::Union{BitVector,Nothing} = nothing; batched::Bool = true) where T<:FT
@@ -934,6 +964,19 @@ function WaveletsExt.Denoising.denoiseall(x::HIP{T,2}, inputtype::Symbol, wt::Or
     bestTH === nothing || (σ = fill(T(bestTH(σ)), length(σ)))               # summary threshold (Denoising.jl:697-700)
     lo = smooth === :undersmooth ? (inputtype === :wpt ? last(coarsestscalingrange(n, tree)) : nodelength(n, L)) : 0
     return iwptall_thresholded(xw, wt, tr, dnt.th, σ; row_lo = lo, scale = dnt.t)
+end
+
+# denoiseall(xw, :swpd | :acwpd, wt; tree::BitMatrix, ...): every signal denoised from its redundant packet table in its own basis (what
+# bestbasistreeall(xw, BB(redundant = true)) returns) by one launch (denoiseall_red_trees above); wt = nothing with :swpd returns x̃
+function WaveletsExt.Denoising.denoiseall(x::HIP{T,3}, inputtype::Symbol, wt::Union{OrthoFilter,Nothing};
+        tree::BitMatrix, dnt = VisuShrink(size(x, 1)), estnoise::Union{Function,Vector{<:Number}} = noisest,
+        bestTH::Union{Function,Nothing} = nothing, smooth::Symbol = :regular) where T<:FT
+    @assert smooth in (:undersmooth, :regular)
+    inputtype in (:swpd, :acwpd) || throw(ArgumentError("a packet table with a tree matrix (one tree per signal) needs inputtype = :swpd or :acwpd"))
+    estnoise isa Function && estnoise !== noisest && throw(ArgumentError("device pipeline: estnoise = noisest or precomputed values"))
+    σ = estnoise isa Function ? (bestTH === nothing ? nothing : noisestall(x, true, tree)) : Vector{T}(estnoise)
+    bestTH === nothing || (σ = T[bestTH(σ)])                                # summary threshold (Denoising.jl:697-700)
+    return denoiseall_red_trees(x, inputtype, wt, tree, dnt.th, dnt.t, smooth === :undersmooth; thr = σ)
 end
 
 # ---------------------------------------------------------------------------------------------------------------------
