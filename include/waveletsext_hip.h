@@ -460,6 +460,62 @@ int wx_wpd_bbtrees_f32(const float *x, int64_t n, int64_t L, int64_t batch, cons
                        float *costs, void *stream);
 int wx_wpd_bb_last_route(void);
 
+/* Per-signal best bases of the redundant decompositions straight from the signals:
+ * bestbasistreeall(swpdall(x, wt, L), BB(cost, redundant = true)) and the same on acwpdall (BestBasis.jl:59-83, 253-262 over tree_costs,
+ * bestbasis/bestbasis_tree.jl:210-233 with the redundant branch :215-220; the tables of SWT.jl:840-868 / swt_all.jl and ACWT.jl:733-759 /
+ * acwt_all.jl, filled by sdwt_step! swt/swt_one_level.jl:99-127 and acdwt_step! acwt/acwt_one_level.jl:101-128) without the
+ * (n, 2^(L+1) - 1, batch) packet table.  x (n, batch) -> trees (n - 1, batch), one byte per node in the layout of wx_treeselect_batch_*
+ * (flags below 2^L - 1, zero above); costs is NULL or receives the (2^(L+1) - 1, batch) costs as tree_costs returns them: a node's
+ * entropy divided by 2^depth, not the ones the selection has folded.  cost_kind as wx_bb_costs_*.  The autocorrelation family is Float64
+ * only, like the reference.  Pointers may be host or device; device calls are asynchronous on `stream`.
+ * Before a device is needed: bad dimensions, NULL x / qmf / trees, another cost_kind -> WX_EARG; n not dyadic or L outside
+ * 0 ... maxtransformlevels(n) -> WX_EASSERT; n >= 2^30 -> WX_EUNSUPPORTED; batch == 0 -> WX_OK with nothing written.
+ * One kernel walks a signal's full tree depth first with the root and two columns per depth, the costs and the selection flags in LDS
+ * (csrc/wx_red_bb.hip: dyadic n >= 8, even filters of 2 ... 20 taps, 160 KiB: Float64 every depth up to n = 512 and depth 8 at 1024,
+ * Float32 depth 10 at 1024); every other shape runs chunks of signals through wx_swpd1d_* / wx_acwpd1d_f64, wx_bb_costs_* (redundant)
+ * and wx_treeselect_batch_* with the chunk's table in scratch of at most 256 MiB (or one signal's table).  The same input gives the
+ * same bytes on every call.
+ * wx_red_bb_last_route: the way the last of these calls (or of wx_denoise_*_sig_trees_* below) went on the calling thread: 0 = none yet, or that call returned an error;
+ * 1 = the fused kernel; 2 = chunks through the table kernels; 3 = nothing to transform (L = 0 or batch = 0). */
+int wx_swpd_bbtrees_f64(const double *x, int64_t n, int64_t L, int64_t batch, const double *qmf, int F, int cost_kind, uint8_t *trees,
+                        double *costs, void *stream);
+int wx_swpd_bbtrees_f32(const float *x, int64_t n, int64_t L, int64_t batch, const double *qmf, int F, int cost_kind, uint8_t *trees,
+                        float *costs, void *stream);
+int wx_acwpd_bbtrees_f64(const double *x, int64_t n, int64_t L, int64_t batch, const double *qmf, int F, int cost_kind, uint8_t *trees,
+                         double *costs, void *stream);
+int wx_red_bb_last_route(void);
+
+/* denoiseall(swpdall(x, wt, L), :swpd, wt; tree, dnt, estnoise, smooth) and denoiseall(acwpdall(x, wt, L), :acwpd, wt; ...) with ONE tree
+ * per signal, straight from the signals x (n, batch): what wx_swpd1d_* / wx_acwpd1d_f64 followed by wx_denoise_swpd1d_trees_* /
+ * wx_denoise_acwpd1d_trees_f64 compute (SWT.jl:840-868, ACWT.jl:733-759; Denoising.jl:228-231, 544-594; Utils.jl:363-367, 428-433),
+ * without the (n, 2^(L+1) - 1, batch) packet table.  For signal b with tree T_b: sigma_b from the column of the finest detail node of
+ * T_b, a chain of at most L high-pass steps from x[:, b]; the leaves of T_b pass threshold(v, th_kind, (T)(sigma_b * scale)), the
+ * coarsest scaling node left alone with undersmooth != 0; out[:, b] = the average-based iswpd (Denoising.jl:561 passes no shift) or
+ * iacwpd along T_b.  x is never modified; out == x returns WX_EARG.  out == NULL: only sigma is computed.  thr != NULL (nthr = 1 or
+ * batch values, host or device): the thresholds before scaling, and nothing is estimated.  sigma (optional, host or device, batch
+ * values): the estimates, or the thresholds used before scaling.  The estimate has the arithmetic of wx_noisest_*; its input column
+ * comes from the same analysis steps in another order of evaluation than the table's, so sigma agrees with the table entries to
+ * rounding, not bit for bit.  trees: (ntree, batch) bytes, host or device, checked and packed as for wx_iswpd1d_trees_*.
+ * Routes (wx_red_bb_last_route): 1 = one launch (csrc/wx_denoise_red_sig.hip: the tree walked depth first with two columns per depth
+ * in LDS; dyadic 8 <= n <= 1024, even filters of 2 .. 20 taps, 2 L n sizeof(T) + the tree bits + 528 bytes <= 160 KiB); 2 = every other
+ * shape, chunks of signals through the table entries above with at most 256 MiB of table in scratch (or one signal's table); 3 = L = 0
+ * (bare roots only: the signal is thresholded) or batch = 0; 0 = the call was refused.
+ * These entries run on the per-signal-tree driver of wx_denoise_swpd1d_trees_*, and route 2 calls those entries: a call also rewrites the
+ * record of wx_wpt_trees_last_route, whose value after it says nothing about this call.
+ * Before a device is needed: bad dimensions, NULL x / qmf / trees, th_kind outside 0 .. 3, nthr not 0, 1 or batch (0 exactly when
+ * thr == NULL), neither out nor sigma, out == x: WX_EARG; n not dyadic, L outside 0 .. maxtransformlevels(n), ntree != n - 1, an invalid
+ * column: WX_EASSERT; a column that decomposes a node of depth >= L: WX_EBOUNDS; n >= 2^30: WX_EUNSUPPORTED.  The lowest offending column
+ * decides; a rejected call has written nothing. */
+int wx_denoise_swpd1d_sig_trees_f64(const double *x, double *out, int64_t n, int64_t L, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                    const double *qmf, int F, int th_kind, double scale, const double *thr, int64_t nthr, int undersmooth,
+                                    double *sigma, void *stream);
+int wx_denoise_swpd1d_sig_trees_f32(const float *x, float *out, int64_t n, int64_t L, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                    const double *qmf, int F, int th_kind, double scale, const float *thr, int64_t nthr, int undersmooth,
+                                    float *sigma, void *stream);
+int wx_denoise_acwpd1d_sig_trees_f64(const double *x, double *out, int64_t n, int64_t L, const uint8_t *trees, int64_t ntree, int64_t batch,
+                                     const double *qmf, int F, int th_kind, double scale, const double *thr, int64_t nthr, int undersmooth,
+                                     double *sigma, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Denoising core -- SURVEY 8(f) row 1: the two device steps between a forward and an inverse batch transform
  * (denoise / denoiseall, Denoising.jl:483-712).  X (n, k, batch) is any coefficient container of this header:

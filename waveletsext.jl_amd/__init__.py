@@ -25,10 +25,12 @@ from .bestbasis import (JBB, LoglpCost, NormCost, tree_costs, bestbasistree, bes
                         jbb_moments, costs_from_moments, acwpd_jbb_moments,
                         BB, ShannonEntropyCost, LogEnergyEntropyCost, bestbasistreeall,
                         LSDB, DifferentialEntropyCost, lsdb_entropy,
-                        wpd_bestbasistreeall, bestbasiscoefall, wpd_bb_route)
+                        wpd_bestbasistreeall, bestbasiscoefall, wpd_bb_route,
+                        swpd_bestbasistreeall, acwpd_bestbasistreeall, red_bb_route)
 from .denoising import (HardTH, SoftTH, SemiSoftTH, SteinTH, VisuShrink, SureShrink, RelErrorShrink,   # noqa: F401,E402
                         noisest, noisestall, threshold, denoise, denoiseall, surethreshold, relerrorthreshold,
-                        surethresholdall, relerrorthresholdall)
+                        surethresholdall, relerrorthresholdall,
+                        swpd_denoiseall, acwpd_denoiseall, red_noisestall, bestbasis_denoiseall)
 from .ldb import (TimeFrequency, AsymmetricRelativeEntropy, SymmetricRelativeEntropy, LpDistance,        # noqa: F401,E402
                   HellingerDistance, EarthMoverDistance, ProbabilityDensity, Signatures, SignatureMap, BasisDiscriminantMeasure,
                   FishersClassSeparability, RobustFishersClassSeparability, energy_map,

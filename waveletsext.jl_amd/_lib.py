@@ -217,6 +217,13 @@ _PLAIN_SIGS = {
     "wx_wpd_bbtrees_f64": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
     "wx_wpd_bbtrees_f32": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
     "wx_wpd_bb_last_route": [],
+    "wx_swpd_bbtrees_f64": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
+    "wx_swpd_bbtrees_f32": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
+    "wx_acwpd_bbtrees_f64": [_P, _L, _L, _L, _P, _I, _I, _P, _P, _P],
+    "wx_red_bb_last_route": [],
+    "wx_denoise_swpd1d_sig_trees_f64": [_P, _P, _L, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
+    "wx_denoise_swpd1d_sig_trees_f32": [_P, _P, _L, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
+    "wx_denoise_acwpd1d_sig_trees_f64": [_P, _P, _L, _L, _P, _L, _L, _P, _I, _I, ctypes.c_double, _P, _L, _I, _P, _P],
     "wx_wavemult_plan_info": [_P, _P],
     "wx_wavemult_plan_destroy": [_P],
     "wx_comm_unique_id": [_P],
@@ -336,6 +343,23 @@ def wpd_bb_route():
     include/waveletsext_hip.h): 0 = none yet, or that call raised; 1 = the fused kernel; 2 = chunks of signals through the table
     kernels; 3 = nothing to transform (L = 0, no signals)"""
     return int(lib().wx_wpd_bb_last_route())
+
+
+def red_bb_route():
+    """which way the last swpd_bestbasistreeall / acwpd_bestbasistreeall / swpd_denoiseall / acwpd_denoiseall / red_noisestall call went on this thread (wx_red_bb_last_route,
+    include/waveletsext_hip.h): 0 = none yet, or that call raised; 1 = the fused kernel; 2 = chunks of signals through the table
+    kernels; 3 = nothing to transform (L = 0, no signals)"""
+    return int(lib().wx_red_bb_last_route())
+
+
+def red_bb_grid(n, L, F, elem_size, ac, which, batch):
+    """csrc/wx_debug.h: the workgroups the kernel of wx_swpd_bbtrees_* / wx_acwpd_bbtrees_f64 (which = 0) or of
+    wx_denoise_swpd1d_sig_trees_* / wx_denoise_acwpd1d_sig_trees_f64 (which = 1) is launched with for this shape, by the functions the
+    launch calls; 0 outside the kernel's window.  Needs no device."""
+    f = lib().wx_debug_red_bb_grid
+    f.argtypes = [_L, _I, _I, _I, _I, _I, _L]
+    f.restype = _I
+    return int(f(int(n), int(L), int(F), int(elem_size), int(bool(ac)), int(which), int(batch)))
 
 
 def wpd_bb_grid(n, L, F, elem_size, batch):

@@ -7,7 +7,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import wpd_bb_route  # noqa: F401
+from ._lib import wpd_bb_route, red_bb_route  # noqa: F401
 from ._arrays import Arg, is_torch, qmf_arg, to_numpy
 from .dwt import _call
 from .filters import ArgumentError
@@ -299,23 +299,15 @@ def acwpd_jbb_moments(x, wt, L=None, accumulate_into=None):
     return s.arr, q.arr
 
 
-def wpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=False):
-    """bestbasistreeall(wpdall(x, wt, L), BB(cost)) (BestBasis.jl:253-262, bestbasis_tree.jl:210-233) straight from the signals
-    x (n, N): the (n, L+1, N) packet table is never written.  Returns what bestbasistreeall returns, a column-major boolean
-    (n-1, N) matrix, or with device=True (x a device tensor) the torch.bool view that wptall / iwptall / denoiseall take as it
-    is; return_costs=True adds the (2^(L+1)-1, N) costs, as tree_costs gives them for every signal."""
-    method = BB() if method is None else method
-    if not isinstance(method, BB):
-        raise TypeError("wpd_bestbasistreeall takes a BB method (BestBasis.jl:253)")
-    if method.redundant:
-        raise TypeError("wpd_bestbasistreeall: redundant tables keep their table, use bestbasistreeall(swpdall(...), BB(redundant=True))")
+def _bbtrees_from_signals(entry, name, x, wt, L, method, device, return_costs):
+    """wx_wpd_bbtrees_* / wx_swpd_bbtrees_* / wx_acwpd_bbtrees_f64 on the signals x (n, N): the trees as bestbasistreeall returns them
+    (host matrix, or the device view with device=True), and the costs on request"""
     if device and not (is_torch(x) and x.device.type != "cpu"):
-        raise TypeError("wpd_bestbasistreeall(..., device=True) takes a device tensor")
+        raise TypeError("%s(..., device=True) takes a device tensor" % name)
     xa = Arg(x)
     assert xa.arr.ndim == 2
     n, N = xa.shape
-    Lmax = maxtransformlevels(n)
-    L = Lmax if L is None else int(L)
+    L = maxtransformlevels(n) if L is None else int(L)
     kind = 0 if isinstance(method.cost, ShannonEntropyCost) else 1
     ntree, ncost = max(n - 1, 0), (1 << (max(L, 0) + 1)) - 1
     costs = xa.new((ncost, N)) if return_costs else None
@@ -327,8 +319,7 @@ def wpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=
         trees = np.empty((N, ntree), dtype=np.uint8)
         tp = ctypes.c_void_p(trees.ctypes.data)
     q, qp, F = qmf_arg(wt)
-    _call("wx_wpd_bbtrees", xa.suffix, xa.ptr, n, L, N, qp, F, kind, tp, costs.ptr if return_costs else ctypes.c_void_p(0),
-          xa.stream())
+    _call(entry, xa.suffix, xa.ptr, n, L, N, qp, F, kind, tp, costs.ptr if return_costs else ctypes.c_void_p(0), xa.stream())
     if device:
         t = trees.T.view(torch.bool)                   # (n-1, N) column-major; the kernel writes bytes of 0 / 1
     elif xa.kind == "torch":
@@ -339,6 +330,42 @@ def wpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=
     else:
         t = trees.T.view(np.bool_)
     return (t, costs.arr) if return_costs else t
+
+
+def wpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=False):
+    """bestbasistreeall(wpdall(x, wt, L), BB(cost)) (BestBasis.jl:253-262, bestbasis_tree.jl:210-233) straight from the signals
+    x (n, N): the (n, L+1, N) packet table is never written.  Returns what bestbasistreeall returns, a column-major boolean
+    (n-1, N) matrix, or with device=True (x a device tensor) the torch.bool view that wptall / iwptall / denoiseall take as it
+    is; return_costs=True adds the (2^(L+1)-1, N) costs, as tree_costs gives them for every signal."""
+    method = BB() if method is None else method
+    if not isinstance(method, BB):
+        raise TypeError("wpd_bestbasistreeall takes a BB method (BestBasis.jl:253)")
+    if method.redundant:
+        raise TypeError("wpd_bestbasistreeall is the decimated transform: BB(redundant=True) goes with swpd_bestbasistreeall / acwpd_bestbasistreeall")
+    return _bbtrees_from_signals("wx_wpd_bbtrees", "wpd_bestbasistreeall", x, wt, L, method, device, return_costs)
+
+
+def _red_bestbasistreeall(entry, name, x, wt, L, method, device, return_costs):
+    method = BB(redundant=True) if method is None else method
+    if not isinstance(method, BB):
+        raise TypeError("%s takes a BB method (BestBasis.jl:253)" % name)
+    if not method.redundant:
+        raise TypeError("%s: the table of a redundant transform takes BB(redundant=True) (bestbasis_tree.jl:215)" % name)
+    return _bbtrees_from_signals(entry, name, x, wt, L, method, device, return_costs)
+
+
+def swpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=False):
+    """bestbasistreeall(swpdall(x, wt, L), BB(cost, redundant=True)) (BestBasis.jl:253-262, bestbasis_tree.jl:210-233) straight from
+    the signals x (n, N), host or device: the (n, 2^(L+1)-1, N) packet table is never written.  Returns what bestbasistreeall
+    returns, a column-major boolean (n-1, N) matrix, or with device=True (x a device tensor) the torch.bool view that iswpdall and
+    denoiseall(xw, "swpd", wt, tree=M) take as it is; return_costs=True adds the (2^(L+1)-1, N) costs, as tree_costs gives them
+    for every signal.  method defaults to BB(redundant=True); red_bb_route() tells which way the call went."""
+    return _red_bestbasistreeall("wx_swpd_bbtrees", "swpd_bestbasistreeall", x, wt, L, method, device, return_costs)
+
+
+def acwpd_bestbasistreeall(x, wt, L=None, method=None, device=False, return_costs=False):
+    """swpd_bestbasistreeall for the autocorrelation packet table acwpdall(x, wt, L); Float64 only, like the transform"""
+    return _red_bestbasistreeall("wx_acwpd_bbtrees", "acwpd_bestbasistreeall", x, wt, L, method, device, return_costs)
 
 
 def bestbasiscoefall(x, wt, L=None, method=None, device=False):

@@ -3,6 +3,7 @@
 #include "../../include/waveletsext_hip.h"
 #include "wx_host.h"
 #include "wx_kernels.h"
+#include "wx_acfilt.h"                         // wx_pack_acfilter
 #include <math.h>
 #include <string.h>
 
@@ -26,21 +27,6 @@ enum { LAYOUT_DWT = 0, LAYOUT_WPT = 1, LAYOUT_WPD = 2 };
 static int64_t wx_ncols(int layout, int L)
 {
     return layout == LAYOUT_DWT ? L + 1 : (layout == LAYOUT_WPT ? ((int64_t)1 << L) : ((int64_t)1 << (L + 1)) - 1);
-}
-
-// acwt_utils.jl:7-48: a_k = 2 sum_i q[i] q[i+k]; b = c2 * a with c1 = 1/sqrt(2), c2 = c1/2
-static void wx_pack_acfilter(const WxFilt &f, WxAcFilt *ac)
-{
-    memset(ac, 0, sizeof *ac);
-    ac->F = f.F;
-    ac->c1 = 1.0 / sqrt(2.0);
-    const double c2 = ac->c1 / 2;
-    for (int k = 1; k <= f.F - 1; ++k) {
-        double r = 0.0;
-        for (int i = 1; i <= f.F - k; ++i) r += f.q[i - 1] * f.q[i + k - 1];
-        r *= 2;
-        ac->b[k - 1] = c2 * r;
-    }
 }
 
 // ---- forward: sdwt / swpt / swpd / acdwt / acwpt / acwpd -----------------------------------

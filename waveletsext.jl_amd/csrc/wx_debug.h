@@ -176,6 +176,13 @@ int wx_debug_ldb_chunks(int64_t nk, int64_t N, int nc);
  * filter of F taps, elem_size 8 / 4 = Float64 / Float32, by the very functions the launch calls; 0 when the shape is outside the
  * kernel's window (the chunked route) or L < 1.  Needs no device. */
 int wx_debug_wpd_bb_grid(int64_t n, int L, int F, int elem_size, int64_t batch);
+
+/* The workgroups of the kernels that start from the signals of a redundant decomposition (wx_red_bb.hip), for `batch` signals of n
+ * samples at depth L under a filter of F taps, elem_size 8 / 4 = Float64 / Float32, ac != 0 = the autocorrelation family (Float64 only),
+ * by the very functions the launch calls; 0 when the shape is outside the kernel's window (the chunked route) or L < 1.  which: 0 = the
+ * trees (wx_swpd_bbtrees_*, wx_acwpd_bbtrees_f64), 1 = the denoising (wx_denoise_swpd1d_sig_trees_*, wx_denoise_acwpd1d_sig_trees_f64,
+ * wx_denoise_red_sig.hip); any other value answers 0.  Needs no device. */
+int wx_debug_red_bb_grid(int64_t n, int L, int F, int elem_size, int ac, int which, int64_t batch);
 #ifdef __cplusplus
 }
 #endif

@@ -29,54 +29,13 @@
 // there is nothing to walk.  k_drt_sigma estimates with one wavefront per signal, four signals per workgroup, no LDS; k_drt_table is the
 // elementwise pass with the per-signal leaf masks, a workgroup per column.
 #include "wx_kernels.h"
-#include "wx_select_count.h"
+#include "wx_red_combine.h"                     // rt_combine
+#include "wx_red_estimate.h"                    // drt_estimate, drt_finest, drt_coarsest, DRT_MAXLOG2N
 #include "wx_trees_host.h"
 
 namespace {
 
-enum { DRT_AVG = 0, DRT_AC = 2 };                                      // the kinds RT_AVG and RT_AC of k_red_trees
-constexpr int DRT_MAXLOG2N = 10;                                       // 16 registers per lane (32 spill in the Float32 kernel)
-
-// sigma of the n = 2^log2n values of `col`, by one whole wavefront (every lane calls): NR = max(1, n / 64) registers per lane
-template <typename T, int NR> __device__ __forceinline__ T drt_mad(const T *__restrict__ col, int n, int lane)
-{
-    double e[NR];
-#pragma unroll
-    for (int u = 0; u < NR; ++u) {
-        const int i = lane + 64 * u;
-        e[u] = i < n ? (double)col[i] : __builtin_inf();
-    }
-    double sg[1];
-    dn_noisest<-1, 64, 1, NR, T>(e, sg, true, n);
-    return (T)sg[0];
-}
-template <typename T> __device__ __forceinline__ T drt_estimate(const T *__restrict__ col, int log2n, int lane)
-{
-    const int n = 1 << log2n;
-    switch (log2n) {                                                   // uniform
-    case 10: return drt_mad<T, 16>(col, n, lane);
-    case 9: return drt_mad<T, 8>(col, n, lane);
-    case 8: return drt_mad<T, 4>(col, n, lane);
-    case 7: return drt_mad<T, 2>(col, n, lane);
-    default: return drt_mad<T, 1>(col, n, lane);
-    }
-}
-
-// the finest detail node of the tree whose words are tg (global or LDS): right children from the root; depth < dmax holds for every tree
-// that passed the check, and keeps the node's column inside the table whatever the words hold
-__device__ __forceinline__ int drt_finest(const uint32_t *tg, int ntree, int dmax)
-{
-    int node = 1;
-    for (int d = 0; node <= ntree && d < dmax && wt_set(tg, node); ++d) node = 2 * node + 1;
-    return node;
-}
-// the coarsest scaling node: left children from the root, the strict `<` of Utils.jl:363-367
-__device__ __forceinline__ int drt_coarsest(const uint32_t *tg, int ntree, int dmax)
-{
-    int node = 1;
-    for (int d = 0; node < ntree && d < dmax && wt_set(tg, node); ++d) node = 2 * node;
-    return node;
-}
+enum { DRT_AVG = RT_AVG, DRT_AC = RT_AC };                             // the kinds of k_red_trees this kernel has (wx_red_combine.h)
 
 // xw: (n, ncols, batch); x: (n, batch); trees: wt_words(n) words of tree bits per signal.  dmax: the deepest tree the table admits (the
 // slots of LDS).  thr != nullptr: the thresholds before scaling (per_thr: one per signal), no estimate.  sigma (optional): batch values.
@@ -156,34 +115,7 @@ __global__ __launch_bounds__(1024) void k_denoise_red_trees(const T *__restrict_
                 const int d = depth;
                 const T *w1 = slots + (size_t)(2 * d) * n, *w2 = w1 + n;
                 T *out = node == 1 ? xs : slots + (size_t)(2 * (d - 1) + (node & 1)) * n;
-                if (KIND == DRT_AC) {
-                    const double sqrt2 = 1.4142135623730951;
-                    for (int p = tid; p < n; p += NT) out[p] = (T)(((double)w1[p] + (double)w2[p]) / sqrt2);
-                } else {
-                    // isdwt_step!(v, w1, w2, d, h, g), swt/swt_one_level.jl:257-277, as k_red_trees' RT_AVG
-                    const int s = 1 << d, np = n >> d, nc = np >> 1;
-                    for (int p = tid; p < n; p += NT) {
-                        const int cls = p & (s - 1), u = p >> d;
-                        double acc = 0.0;
-                        for (int var = 0; var <= 1; ++var) {
-                            const int swc = cls + var * s;
-                            const int t0 = var ? u : (u + 1 == np ? 0 : u + 1);
-                            const bool odd = t0 & 1;
-                            int k1 = t0 >> 1, k2 = k1;
-                            double v = 0.0;
-                            for (int m = 0; m < F / 2; ++m) {
-                                const double a = (double)w1[swc + k1 * 2 * s], c = (double)w2[swc + k2 * 2 * s];
-                                const double q0 = qs[2 * m], q1 = qs[2 * m + 1];
-                                v = fma(odd ? q1 : q0, a, v);
-                                v = fma(odd ? q0 : -q1, c, v);
-                                k1 = k1 == 0 ? nc - 1 : k1 - 1;
-                                k2 = k2 + 1 == nc ? 0 : k2 + 1;
-                            }
-                            acc += v;
-                        }
-                        out[p] = (T)(acc * 0.5);
-                    }
-                }
+                rt_combine<T, KIND>(w1, w2, out, n, d, 0, F, qs, tid, NT);
                 read = true;
             }
             if (node == 1) break;

@@ -17,7 +17,7 @@
 // control flow.  A barrier stands before every combine (its children are complete, and the slot it writes has been read) and before a
 // leaf load that follows a combine.  No scratch memory, no atomics: every leaf element is read from HBM once, every element of x is written
 // once, by one lane.
-// Combines, one lane per parent position p, d = the parent's depth, s = 2^d, u = p >> d, np = n >> d:
+// Combines (rt_combine, wx_red_combine.h), one lane per parent position p, d = the parent's depth, s = 2^d, u = p >> d, np = n >> d:
 //   SWT average (sm < 0)   isdwt_step!(v, w1, w2, d, h, g), swt/swt_one_level.jl:257-277: the reconstruction from the children's class
 //                          p mod s (t0 = u + 1 mod np) plus the one from the class shifted by s (t0 = u), halved; either sum runs over the
 //                          taps in the reference's order (:305-316, with `m-1<<d` read as m - (1 << d)), in Float64 with fma, the child
@@ -33,11 +33,10 @@
 // (of 160): Float64 takes every depth up to n = 512 and depth 8 at n = 1024 (depth 9 needs 144 KiB).  Outside it the driver runs the
 // single-tree entry once per signal; byte-identical columns go to the single-tree entry whole (wx_trees_host.h).
 #include "wx_kernels.h"
+#include "wx_red_combine.h"                     // RT_AVG, RT_SHIFT, RT_AC, rt_combine
 #include "wx_trees_host.h"
 
 namespace {
-
-enum { RT_AVG = 0, RT_SHIFT = 1, RT_AC = 2 };
 
 // xw: (n, ncols, batch); x: (n, batch); trees: wt_words(n) words of tree bits per signal.  dmax: the deepest tree the table admits (the
 // slots of LDS).  LDS: WX_MAXF doubles | 2 dmax columns of n elements | the tree's words.
@@ -96,37 +95,7 @@ __global__ __launch_bounds__(1024) void k_red_trees(const T *__restrict__ xw, T 
                 const int d = depth;
                 const T *w1 = slots + (size_t)(2 * d) * n, *w2 = w1 + n;
                 T *out = node == 1 ? xs : slots + (size_t)(2 * (d - 1) + (node & 1)) * n;
-                if (KIND == RT_AC) {
-                    const double sqrt2 = 1.4142135623730951;
-                    for (int p = tid; p < n; p += NT) out[p] = (T)(((double)w1[p] + (double)w2[p]) / sqrt2);
-                } else {
-                    const int s = 1 << d, np = n >> d, nc = np >> 1;
-                    const int sv = sm & (s - 1);                       // main2depthshift: sd[d]; sd[d + 1] = sv or sv + s
-                    const int shifted = (sm >> d) & 1;
-                    for (int p = tid; p < n; p += NT) {
-                        const int cls = p & (s - 1), u = p >> d;
-                        if (KIND == RT_SHIFT && cls != sv) { out[p] = (T)0; continue; }   // never the root: s = 1 there
-                        double acc = 0.0;
-                        for (int var = (KIND == RT_SHIFT ? shifted : 0); var <= (KIND == RT_SHIFT ? shifted : 1); ++var) {
-                            // var 0: sw == sv, parent sample t0 sits at class position t0 - 1; var 1: sw == sv + s
-                            const int swc = cls + var * s;
-                            const int t0 = var ? u : (u + 1 == np ? 0 : u + 1);
-                            const bool odd = t0 & 1;
-                            int k1 = t0 >> 1, k2 = k1;
-                            double v = 0.0;
-                            for (int m = 0; m < F / 2; ++m) {
-                                const double a = (double)w1[swc + k1 * 2 * s], c = (double)w2[swc + k2 * 2 * s];
-                                const double q0 = qs[2 * m], q1 = qs[2 * m + 1];
-                                v = fma(odd ? q1 : q0, a, v);
-                                v = fma(odd ? q0 : -q1, c, v);
-                                k1 = k1 == 0 ? nc - 1 : k1 - 1;
-                                k2 = k2 + 1 == nc ? 0 : k2 + 1;
-                            }
-                            acc += v;
-                        }
-                        out[p] = (T)(KIND == RT_AVG ? acc * 0.5 : acc);
-                    }
-                }
+                rt_combine<T, KIND>(w1, w2, out, n, d, sm, F, qs, tid, NT);
                 read = true;
             }
             if (node == 1) break;

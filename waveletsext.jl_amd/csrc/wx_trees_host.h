@@ -22,11 +22,16 @@
 //   int64_t in_count()                 elements of one input item
 //   int tree_k()                       no tree may be as deep as this: the `k` of the trees' check, whatever the mode
 //   int too_deep()                     the error of a tree that is, with the code and message of the shape's single-tree entry
+// A shape with `static constexpr bool by_chunks = true` has no single-tree entry to fall back on (wx_denoise_red_sig.hip: the items are signals,
+// the table entries want tables): inside the window the kernel runs whether the columns are equal or not, and outside it
+//   int chunked(x, y, trees, ...)      runs the whole checked batch, the tree matrix in host memory, by a loop of its own
+// replaces single() once per item.
 #pragma once
 #include "../../include/waveletsext_hip.h"
 #include "wx_common.h"
 #include "wx_host.h"
 #include "wx_tree_bits.h"
+#include "wx_trees_geom.h"                      // wx_trees_threads, wx_trees_grid
 #include "wx_trees_prep.h"
 #include <type_traits>
 #include <vector>
@@ -42,6 +47,8 @@ template <typename S, typename = void> struct WxTreesExtras { static constexpr b
 template <typename S> struct WxTreesExtras<S, std::void_t<decltype(S::extras)>> { static constexpr bool value = S::extras; };
 template <typename S, typename = void> struct WxTreesTable { static constexpr bool value = false; };
 template <typename S> struct WxTreesTable<S, std::void_t<decltype(S::table)>> { static constexpr bool value = S::table; };
+template <typename S, typename = void> struct WxTreesChunked { static constexpr bool value = false; };
+template <typename S> struct WxTreesChunked<S, std::void_t<decltype(S::by_chunks)>> { static constexpr bool value = S::by_chunks; };
 
 // elements of one input item, and the depth no tree may reach (0: any)
 template <int MODE, typename S> inline int64_t wx_trees_in_count(const S &s, int k)
@@ -53,25 +60,6 @@ template <int MODE, typename S> inline int wx_trees_k(const S &s, int k)
 {
     if constexpr (WxTreesTable<S>::value) return s.tree_k();
     else return MODE == WX_TREES_IWPD ? k : 0;
-}
-
-// one lane per output pair of a level or pass, at most 1024
-inline int wx_trees_threads(int64_t count)
-{
-    int nt = 64;
-    while (nt < 1024 && nt < count / 2) nt <<= 1;
-    return nt;
-}
-
-// workgroups resident on the 256 CUs (160 KiB of LDS and 2048 lanes each, at most 16 workgroups), never more than items
-inline int wx_trees_grid(size_t lds, int nt, int64_t batch)
-{
-    int per_cu = (int)((160 * 1024) / lds);
-    if (per_cu > 2048 / nt) per_cu = 2048 / nt;
-    if (per_cu > 16) per_cu = 16;
-    if (per_cu < 1) per_cu = 1;
-    const int64_t g = (int64_t)256 * per_cu;
-    return (int)(g < batch ? g : batch);
 }
 
 // trees in host memory
@@ -96,16 +84,21 @@ int wx_trees_from_host(const S &s, const T *x, T *y, int k, const uint8_t *trees
     if (rc) return rc;
     if (batch == 0) return WX_OK;
     if (wx_device_count() < 1) return wx_set_error(WX_EHIP, "no HIP device visible: the MI355X kernels cannot run");
-    // one tree after all: the single-tree entry has the lattice kernels and the register kernels of 64 x 64 images
-    if (same) return s.single(MODE, x, y, k, trees, ntree, batch, qmf, F, stream);
-    // outside the LDS kernel's window: the single-tree path once per item.  Slow (a tree upload and a launch sequence per item).
-    if (!lds_path) {
-        for (int64_t b = 0; b < batch; ++b) {
-            if constexpr (WxTreesExtras<S>::value) rc = s.at(b).single(MODE, x + b * xs, y ? y + b * cnt : y, k, trees + b * ntree, ntree, 1, qmf, F, stream);
-            else rc = s.single(MODE, x + b * xs, y + b * cnt, k, trees + b * ntree, ntree, 1, qmf, F, stream);
-            if (rc) return rc;
+    if constexpr (WxTreesChunked<S>::value) {
+        if (!lds_path) return s.chunked(x, y, trees, ntree, batch, qmf, F, stream);
+    } else {
+        // one tree after all: the single-tree entry has the lattice kernels and the register kernels of 64 x 64 images
+        if (same) return s.single(MODE, x, y, k, trees, ntree, batch, qmf, F, stream);
+        // outside the LDS kernel's window: the single-tree path once per item.  Slow (a tree upload and a launch sequence per item).
+        if (!lds_path) {
+            for (int64_t b = 0; b < batch; ++b) {
+                if constexpr (WxTreesExtras<S>::value)
+                    rc = s.at(b).single(MODE, x + b * xs, y ? y + b * cnt : y, k, trees + b * ntree, ntree, 1, qmf, F, stream);
+                else rc = s.single(MODE, x + b * xs, y + b * cnt, k, trees + b * ntree, ntree, 1, qmf, F, stream);
+                if (rc) return rc;
+            }
+            return WX_OK;
         }
-        return WX_OK;
     }
     hipStream_t st = wx_stream(stream);
     WxScratch scr(st);
@@ -172,10 +165,12 @@ int wx_trees_from_device(const S &s, const T *x, T *y, int k, const uint8_t *tre
     if constexpr (WxTreesTable<S>::value)
         if (rc == WX_EARG) return s.too_deep();
     if (rc) return rc;                                                 // nothing has been written to y
-    if (same) {                                                        // one tree after all: as the host path does, with the same result
-        rc = s.single(MODE, x, y, k, col0.data(), ntree, batch, qmf, F, stream);
-        if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_SINGLE);
-        return rc;
+    if constexpr (!WxTreesChunked<S>::value) {
+        if (same) {                                                    // one tree after all: as the host path does, with the same result
+            rc = s.single(MODE, x, y, k, col0.data(), ntree, batch, qmf, F, stream);
+            if (rc == WX_OK) wx_trees_route_set(WX_TREES_ROUTE_DEV_SINGLE);
+            return rc;
+        }
     }
     WxIO io(st);
     const T *dx = (const T *)io.in(x, sizeof(T) * wx_trees_in_count<MODE>(s, k) * batch);

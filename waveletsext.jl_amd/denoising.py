@@ -279,6 +279,85 @@ def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batc
     return _trees_call(xa, N, wt, trees, dnt.th.kind, dnt.t, thr, smooth, True, False, inputtype)[0].arr
 
 
+def _red_sig_call(xa, wt, trees, L, transform, th_kind, scale, thr, smooth, want_out, want_sigma):
+    """wx_denoise_swpd1d_sig_trees_* / wx_denoise_acwpd1d_sig_trees_f64: (xhat | None, sigma | None) as Args of the signals' kind"""
+    from ._arrays import qmf_arg, trees_arg
+    if transform not in ("swpd", "acwpd"):
+        raise ValueError("transform: \"swpd\" or \"acwpd\"")
+    if xa.arr.ndim != 2:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals, (n, N)")
+    null = ctypes.c_void_p(0)
+    n, N = xa.shape
+    L = maxtransformlevels(n) if L is None else int(L)
+    q, qp, F = qmf_arg(wt)
+    tb, tp, nt = trees_arg(trees, N, xa)
+    out = xa.new((n, N)) if want_out else None
+    sig = xa.new((N,)) if want_sigma else None
+    tv = None if thr is None else np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=xa.dtype)))
+    name = ("wx_denoise_swpd1d_sig_trees" if transform == "swpd" else "wx_denoise_acwpd1d_sig_trees") + xa.suffix
+    fn = getattr(_lib.lib(), name, None)
+    if fn is None:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "the autocorrelation transforms are Float64 only")
+    _lib.check(fn(xa.ptr, out.ptr if want_out else null, n, L, tp, nt, N, qp, F, int(th_kind), float(scale),
+                  null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
+                  1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream()))
+    return out, sig
+
+
+def _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, transform):
+    xa = Arg(x)
+    dnt = VisuShrink(xa.shape[0]) if dnt is None else dnt
+    if estnoise is None or estnoise is noisest:
+        thr = None
+    elif estnoise is relerrorthreshold or estnoise is surethreshold:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant basis: the selections "
+                                                 "have no per-signal leaf masks")
+    elif callable(estnoise):
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED,
+                           "noise estimates on the device path: noisest, relerrorthreshold, surethreshold or precomputed values")
+    else:
+        thr = np.broadcast_to(np.asarray(estnoise, dtype=np.float64), (xa.shape[-1],)).astype(xa.dtype)
+    if bestTH is not None:                                             # one summary threshold for the batch, Denoising.jl:697-700
+        if thr is None:
+            thr = to_numpy(_red_sig_call(xa, wt, trees, L, transform, dnt.th.kind, dnt.t, None, smooth, False, True)[1].arr)
+        thr = np.full(1, bestTH(np.asarray(thr, dtype=np.float64)), dtype=xa.dtype)
+    return _red_sig_call(xa, wt, trees, L, transform, dnt.th.kind, dnt.t, thr, smooth, True, False)[0].arr
+
+
+def swpd_denoiseall(x, wt, trees, L=None, dnt=None, estnoise=None, bestTH=None, smooth="regular"):
+    """denoiseall(swpdall(x, wt, L), "swpd", wt, tree=trees, ...) straight from the signals x (n, N), host or device, with the tree of
+    signal i in column i of `trees` ((n - 1, N), host or device: what swpd_bestbasistreeall returns): the (n, 2^(L+1)-1, N) packet table
+    is never written (csrc/wx_denoise_red_sig.hip).  No tree may decompose a node of depth >= L (IndexError).  dnt, estnoise (None /
+    noisest / numbers), bestTH and smooth as denoiseall with a tree matrix."""
+    return _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, "swpd")
+
+
+def acwpd_denoiseall(x, wt, trees, L=None, dnt=None, estnoise=None, bestTH=None, smooth="regular"):
+    """swpd_denoiseall for the autocorrelation packet decomposition acwpdall(x, wt, L); Float64 only, like the transform"""
+    return _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, "acwpd")
+
+
+def red_noisestall(x, wt, trees, L=None, transform="swpd"):
+    """noisestall(swpdall | acwpdall(x, wt, L), True, trees) straight from the signals: every signal's estimate from the finest detail node
+    of its own tree, a chain of at most L high-pass steps"""
+    return _red_sig_call(Arg(x), wt, trees, L, transform, 0, 1.0, None, "regular", False, True)[1].arr
+
+
+def bestbasis_denoiseall(x, wt, L=None, transform="swpd", method=None, **denoise_kw):
+    """swpd_denoiseall(x, wt, swpd_bestbasistreeall(x, wt, L, method), L, ...) (or the acwpd pair): every signal denoised in its own
+    translation-invariant best basis.  With device signals the trees stay on the device."""
+    from .bestbasis import swpd_bestbasistreeall, acwpd_bestbasistreeall
+    if transform not in ("swpd", "acwpd"):
+        raise ValueError("transform: \"swpd\" or \"acwpd\"")
+    extra = set(denoise_kw) - {"dnt", "estnoise", "bestTH", "smooth"}
+    if extra:
+        raise TypeError("bestbasis_denoiseall: unexpected keyword arguments %s" % sorted(extra))
+    dev = is_torch(x) and x.device.type != "cpu"
+    trees = (swpd_bestbasistreeall if transform == "swpd" else acwpd_bestbasistreeall)(x, wt, L, method, device=dev)
+    return _red_denoiseall(x, wt, trees, L, denoise_kw.get("dnt"), denoise_kw.get("estnoise"), denoise_kw.get("bestTH"),
+                           denoise_kw.get("smooth", "regular"), transform)
+
+
 def noisestall(x, redundant=False, tree=None):
     """noisest (Denoising.jl:214-232) of every signal of a batch (last axis): `tree` is None, one tree for all, or an (n - 1, N) matrix with
     the tree of signal i in column i (then each estimate comes from the finest detail node of its own tree; redundant: x is the

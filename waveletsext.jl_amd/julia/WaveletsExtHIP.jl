@@ -780,6 +780,29 @@ function wpd_bestbasistreeall(x::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtran
 end
 "the way the last wpd_bestbasistreeall call went on this thread (wx_wpd_bb_last_route, include/waveletsext_hip.h)"
 wpd_bb_route() = (:none, :fused, :chunked, :trivial)[Int(wx_wpd_bb_last_route()) + 1]
+# swpdall / acwpdall + bestbasistreeall(BB(redundant = true)) fused: what `bestbasistreeall(swpdall(x, wt, L), BB(cost, redundant = true))`
+# returns, straight from the signals -- the (n, 2^(L+1)-1, N) table is never written (wx_swpd_bbtrees_* / wx_acwpd_bbtrees_f64: one kernel
+# walks a signal's full tree depth first with two columns per depth, the costs and the flags in LDS; chunks of signals through the table
+# kernels outside its window).  device and costs as wpd_bestbasistreeall.
+function red_bestbasistreeall(ac::Bool, x::HIP{T,2}, wt::OrthoFilter, L::Integer, method::BB, device::Bool, costs::Bool) where T<:FT
+    method.redundant || throw(ArgumentError("the table of a redundant transform takes BB(redundant = true)"))
+    n, N = size(x); q = qmfvec(wt)
+    trees = device ? newlike(x, UInt8, (max(n - 1, 0), N)) : Matrix{UInt8}(undef, max(n - 1, 0), N)
+    c = !costs ? C_NULL : (device ? newlike(x, T, ((1 << (L + 1)) - 1, N)) : Matrix{T}(undef, (1 << (L + 1)) - 1, N))
+    if ac
+        check(wx_acwpd_bbtrees(Float64, raw(x), n, L, N, q, length(q), bbkind(method.cost), trees, c, stream()))
+    else
+        check(wx_swpd_bbtrees(T, raw(x), n, L, N, q, length(q), bbkind(method.cost), trees, c, stream()))
+    end
+    t = device ? HIP(trees) : BitMatrix(trees .!= 0)
+    return costs ? (t, c) : t
+end
+swpd_bestbasistreeall(x::HIP{T,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(size(x, 1)), method::BB = BB(redundant = true);
+                      device::Bool = false, costs::Bool = false) where T<:FT = red_bestbasistreeall(false, x, wt, L, method, device, costs)
+acwpd_bestbasistreeall(x::HIP{Float64,2}, wt::OrthoFilter, L::Integer = maxtransformlevels(size(x, 1)), method::BB = BB(redundant = true);
+                       device::Bool = false, costs::Bool = false) = red_bestbasistreeall(true, x, wt, L, method, device, costs)
+"the way the last swpd_/acwpd_bestbasistreeall, swpd_/acwpd_denoiseall or red_noisestall call went on this thread (wx_red_bb_last_route)"
+red_bb_route() = (:none, :fused, :chunked, :trivial)[Int(wx_red_bb_last_route()) + 1]
 
 # acwpdall + JBB fused (BASELINE config 5): what `bestbasistree(acwpdall(x, wt, L), JBB(redundant = true))` returns,
 # without the (n, 2^(L+1)-1, N) table -- 16 TiB for 262144 signals of 2048 samples.  The library walks the batch in
@@ -907,6 +930,54 @@ function noisestall(xw::HIP{T,3}, redundant::Bool, trees::BitMatrix) where T<:FT
     sigma = Vector{T}(undef, N); tb = Matrix{UInt8}(trees)
     check(wx_denoise_swpd1d_trees(T, raw(xw), C_NULL, n, k, tb, size(tb, 1), N, C_NULL, 0, 0, 1.0, C_NULL, 0, 0, sigma, stream()))
     return sigma
+end
+# denoiseall(swpdall | acwpdall(x, wt, L), :swpd | :acwpd, wt; tree = trees, ...) with one tree per signal straight from the signals x (n, N):
+# the packet table is never written (wx_denoise_swpd1d_sig_trees_* / wx_denoise_acwpd1d_sig_trees_f64).  σᵢ = noisest on the finest detail
+# node of treeᵢ, or σ = thr (one value, or one per signal); no tree may decompose a node of depth ≥ L.
+function red_sig_trees(ac::Bool, x::HIP{T,2}, x̂, wt::OrthoFilter, trees, L::Integer, th::THType, t::Real, undersmooth::Bool, thr, sigma) where T<:FT
+    n, N = size(x)
+    @assert size(trees, 2) == N
+    tb = trees isa BitMatrix ? Matrix{UInt8}(trees) : raw(trees)
+    q = qmfvec(wt)
+    tv = thr === nothing ? C_NULL : thr; ntv = thr === nothing ? 0 : length(thr)
+    if ac
+        check(wx_denoise_acwpd1d_sig_trees(Float64, raw(x), x̂, n, L, tb, size(tb, 1), N, q, length(q), thkind(th), Float64(t), tv, ntv,
+                                           undersmooth ? 1 : 0, sigma, stream()))
+    else
+        check(wx_denoise_swpd1d_sig_trees(T, raw(x), x̂, n, L, tb, size(tb, 1), N, q, length(q), thkind(th), Float64(t), tv, ntv,
+                                          undersmooth ? 1 : 0, sigma, stream()))
+    end
+end
+function swpd_denoiseall(x::HIP{T,2}, wt::OrthoFilter, trees::Union{BitMatrix,HIP{UInt8,2}}, th::THType, t::Real, undersmooth::Bool = false;
+                         L::Integer = maxtransformlevels(size(x, 1)), thr::Union{Vector{T},Nothing} = nothing) where T<:FT
+    x̂ = newlike(x, T, size(x))
+    red_sig_trees(false, x, x̂, wt, trees, L, th, t, undersmooth, thr, C_NULL)
+    return x̂
+end
+function acwpd_denoiseall(x::HIP{Float64,2}, wt::OrthoFilter, trees::Union{BitMatrix,HIP{UInt8,2}}, th::THType, t::Real, undersmooth::Bool = false;
+                          L::Integer = maxtransformlevels(size(x, 1)), thr::Union{Vector{Float64},Nothing} = nothing)
+    x̂ = newlike(x, Float64, size(x))
+    red_sig_trees(true, x, x̂, wt, trees, L, th, t, undersmooth, thr, C_NULL)
+    return x̂
+end
+"noisest of every signal on the finest detail node of its own tree of the redundant decomposition, straight from the signals"
+function red_noisestall(x::HIP{T,2}, wt::OrthoFilter, trees::Union{BitMatrix,HIP{UInt8,2}}; L::Integer = maxtransformlevels(size(x, 1)),
+                        transform::Symbol = :swpd) where T<:FT
+    transform in (:swpd, :acwpd) || throw(ArgumentError("transform: :swpd or :acwpd"))
+    sigma = Vector{T}(undef, size(x, 2))
+    red_sig_trees(transform === :acwpd, x, C_NULL, wt, trees, L, HardTH(), 1.0, false, nothing, sigma)
+    return sigma
+end
+"swpd_/acwpd_denoiseall along swpd_/acwpd_bestbasistreeall(x, wt, L, method; device = true): the trees never leave the array's kind"
+function bestbasis_denoiseall(x::HIP{T,2}, wt::OrthoFilter, th::THType, t::Real, undersmooth::Bool = false;
+                              L::Integer = maxtransformlevels(size(x, 1)), transform::Symbol = :swpd, method::BB = BB(redundant = true),
+                              thr::Union{Vector{T},Nothing} = nothing) where T<:FT
+    transform in (:swpd, :acwpd) || throw(ArgumentError("transform: :swpd or :acwpd"))
+    ac = transform === :acwpd
+    trees = red_bestbasistreeall(ac, x, wt, L, method, true, false)
+    x̂ = newlike(x, T, size(x))
+    red_sig_trees(ac, x, x̂, wt, trees, L, th, t, undersmooth, thr, C_NULL)
+    return x̂
 end
 # surethreshold / relerrorthreshold of one signal (Denoising.jl:146-166, 285-327) and of every signal of a batch (what
 # SureShrink(xw, redundant, tree) and denoiseall(...; estnoise = relerrorthreshold) evaluate signal by signal)
