@@ -657,6 +657,34 @@ int wx_relerrorthreshold_f64(const double *X, int64_t n, int64_t k, int64_t batc
 int wx_relerrorthreshold_f32(const float *X, int64_t n, int64_t k, int64_t batch, const uint8_t *colmask, int elbows,
                              float *t, void *stream);
 
+/* The two selections on a redundant packet table with ONE tree per signal: t[b] = surethreshold(xw[:, :, b], true, trees[:, b])
+ * (Denoising.jl:146-166) or relerrorthreshold(xw[:, :, b], true, trees[:, b], elbows) (Denoising.jl:285-327), i.e. over all n rows of the
+ * leaf columns of signal b's own tree, coef[:, getleaf(tree)] (Denoising.jl:150-157, 293-300).  The reference takes a single BitVector;
+ * this is its loop with the (ntree, batch) convention of getbasiscoefall (Utils.jl:199-225), as wx_denoise_swpd1d_trees_*, whose `thr`
+ * these are for denoiseall(...; tree = M, estnoise = relerrorthreshold | surethreshold) (test/denoising.jl:59-83).
+ * xw: (n, ncols, batch), the heap-ordered table of swpdall / acwpdall (node i in column i - 1), never modified; the selection does not
+ * care which transform filled it, so the _f64 entries serve :acwpd too.  trees: (ntree, batch) bytes, ntree = n - 1, checked and packed
+ * exactly as for wx_denoise_swpd1d_trees_* (the lowest offending column decides; a rejected call has written nothing).  t: batch values.
+ * xw, trees and t may each be host or device memory.
+ * Signal b ranks cnt_b = n leaves_b coefficients, sorted in a window padded to its own power of two; the arithmetic is that of
+ * wx_surethreshold_* / wx_relerrorthreshold_*, so t[b] is bit for bit what those return for signal b alone with the leaf mask of its tree.
+ * Routes (csrc/wx_shrink_trees.hip): one launch lists every signal's leaf columns and count, one groups the signals by window size, and 128
+ * bytes of group sizes come back to the host (one wait); windows of (2 npad + 8) sizeof(T) <= 144 KiB are sorted in LDS, a workgroup per
+ * signal; larger ones in global scratch (at most 128 MiB of windows at a time, or one window) by bitonic launches over the whole chip that
+ * serve every signal of a size group at once.  Byte-identical columns go to the single-tree entry whole.  The tree matrix is never copied to
+ * the host and nothing loops over signals there.  wx_wpt_trees_last_route reports the route.
+ * Before a device is needed: bad dimensions, NULL trees, NULL t: WX_EARG; elbows < 1, n not dyadic, ntree != n - 1, an invalid column:
+ * WX_EASSERT; a column deeper than the table (2^(depth + 1) - 1 > ncols): WX_EBOUNDS; more than 2^27 coefficients for the deepest tree the
+ * table admits: WX_EUNSUPPORTED.  batch == 0 is WX_OK. */
+int wx_surethreshold_trees_f64(const double *xw, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch, double *t,
+                               void *stream);
+int wx_surethreshold_trees_f32(const float *xw, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch, float *t,
+                               void *stream);
+int wx_relerrorthreshold_trees_f64(const double *xw, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch, int elbows,
+                                   double *t, void *stream);
+int wx_relerrorthreshold_trees_f32(const float *xw, int64_t n, int64_t ncols, const uint8_t *trees, int64_t ntree, int64_t batch, int elbows,
+                                   float *t, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * Local Discriminant Basis, the batch-sized steps -- SURVEY 8(f) row 2.
  * wx_energy_map_*: energy_map(Xw, y, TimeFrequency()) ldb/ldb_energymap.jl:109-141.  Xw is a packet table

@@ -202,6 +202,10 @@ _PLAIN_SIGS = {
     "wx_surethreshold_f32": [_P, _L, _L, _L, _P, _P, _P],
     "wx_relerrorthreshold_f64": [_P, _L, _L, _L, _P, _I, _P, _P],
     "wx_relerrorthreshold_f32": [_P, _L, _L, _L, _P, _I, _P, _P],
+    "wx_surethreshold_trees_f64": [_P, _L, _L, _P, _L, _L, _P, _P],
+    "wx_surethreshold_trees_f32": [_P, _L, _L, _P, _L, _L, _P, _P],
+    "wx_relerrorthreshold_trees_f64": [_P, _L, _L, _P, _L, _L, _I, _P, _P],
+    "wx_relerrorthreshold_trees_f32": [_P, _L, _L, _P, _L, _L, _I, _P, _P],
     "wx_bb_costs_f64": [_P, _P, _L, _L, _L, _I, _I, _P],
     "wx_bb_costs_f32": [_P, _P, _L, _L, _L, _I, _I, _P],
     "wx_bb_costs2d_f64": [_P, _P, _L, _L, _L, _L, _I, _I, _P],

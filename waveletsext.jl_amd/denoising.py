@@ -94,6 +94,25 @@ def _select(xa, batched, redundant, tree, kind, elbows=2):
     return out
 
 
+def _select_trees(xa, trees, kind, elbows=2):
+    """wx_surethreshold_trees_* (kind 0) / wx_relerrorthreshold_trees_* (kind 1): the threshold of every signal over the leaf columns of
+    its own tree in its redundant packet table (csrc/wx_shrink_trees.hip); an Arg of the table's kind with N values, on the device for a
+    device table (nothing is copied to the host, the call waits only for the 128 bytes of group sizes)"""
+    from ._arrays import trees_arg
+    if xa.arr.ndim != 3:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals: an (n, ncols, N) packet table")
+    n, k, N = xa.shape
+    tb, tp, nt = trees_arg(trees, N, xa)
+    out = xa.new((N,))
+    if kind == 0:
+        fn = getattr(_lib.lib(), "wx_surethreshold_trees" + xa.suffix)
+        _lib.check(fn(xa.ptr, n, k, tp, nt, N, out.ptr, xa.stream()))
+    else:
+        fn = getattr(_lib.lib(), "wx_relerrorthreshold_trees" + xa.suffix)
+        _lib.check(fn(xa.ptr, n, k, tp, nt, N, int(elbows), out.ptr, xa.stream()))
+    return out
+
+
 def surethreshold(coef, redundant, tree=None):
     """surethreshold(coef, redundant[, tree]) Denoising.jl:146-166 for one decomposed signal"""
     return float(_select(Arg(coef), False, redundant, tree, 0)[0])
@@ -106,13 +125,20 @@ def relerrorthreshold(coef, redundant=False, tree=None, elbows=2):
 
 
 def surethresholdall(coef, redundant, tree=None):
-    """surethreshold of every signal of a batch (last axis), one launch"""
+    """surethreshold of every signal of a batch (last axis), one launch.  redundant with `tree` an (n - 1, N) matrix, host or device:
+    coef is the (n, ncols, N) packet table of swpdall / acwpdall (numpy or a device tensor) and signal i is selected over the leaf
+    columns of column i of `tree`; the N thresholds come back as the table's kind (a device tensor for a device table)"""
+    if redundant and _is_tree_matrix(tree):
+        return _select_trees(Arg(coef), tree, 0).arr
     return _select(Arg(coef), True, redundant, tree, 0)
 
 
 def relerrorthresholdall(coef, redundant=False, tree=None, elbows=2):
     """relerrorthreshold of every signal of a batch (last axis), one launch: what denoiseall evaluates signal by
-    signal when estnoise = relerrorthreshold (Denoising.jl:676-680)"""
+    signal when estnoise = relerrorthreshold (Denoising.jl:676-680).  redundant with `tree` an (n - 1, N) matrix: one tree per
+    signal, as surethresholdall"""
+    if redundant and _is_tree_matrix(tree):
+        return _select_trees(Arg(coef), tree, 1, elbows).arr
     return _select(Arg(coef), True, redundant, tree, 1, elbows)
 
 
@@ -211,10 +237,20 @@ def _is_tree_matrix(tree):
     return tree is not None and np.ndim(tree) == 2
 
 
+def _thr_arg(thr, dtype):
+    """(buffer kept alive, pointer, count) of the thresholds of a per-signal-tree entry: None, host values, or an Arg (a device pointer)"""
+    if thr is None:
+        return None, ctypes.c_void_p(0), 0
+    if isinstance(thr, Arg):
+        return thr, thr.ptr, int(np.prod(thr.shape))
+    tv = np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=dtype)))
+    return tv, ctypes.c_void_p(tv.ctypes.data), tv.size
+
+
 def _trees_call(xa, N, wt, trees, th_kind, scale, thr, smooth, want_out, want_sigma, inputtype="wpt"):
     """wx_denoise_wpt1d_trees_* / wx_denoise_swpd1d_trees_* / wx_denoise_acwpd1d_trees_f64: (xhat | None, sigma | None) as Args of the input's
-    kind; thr: None (the noise is estimated per signal, each on the finest detail node of its own tree) or 1 / N host values, the thresholds
-    before scaling.  A redundant table (n, ncols, N) gives (n, N) signals, or with :swpd and wt = None the thresholded table"""
+    kind; thr: None (the noise is estimated per signal, each on the finest detail node of its own tree), 1 / N host values, or an Arg on the
+    device (what _select_trees left there): the thresholds before scaling.  A redundant table (n, ncols, N) gives (n, N) signals, or with :swpd and wt = None the thresholded table"""
     from ._arrays import qmf_arg, trees_arg
     null = ctypes.c_void_p(0)
     q, qp, F = (None, null, 0) if wt is None else qmf_arg(wt)
@@ -226,9 +262,8 @@ def _trees_call(xa, N, wt, trees, th_kind, scale, thr, smooth, want_out, want_si
         oshape = (n,) + tuple(xa.shape[2:])                            # (n, ncols[, N]) -> (n[, N])
     out = xa.new(oshape) if want_out else None
     sig = xa.new((N,)) if want_sigma else None
-    tv = None if thr is None else np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=xa.dtype)))
-    tail = (int(th_kind), float(scale), null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
-            1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream())
+    tv, tvp, tvn = _thr_arg(thr, xa.dtype)
+    tail = (int(th_kind), float(scale), tvp, tvn, 1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream())
     optr = out.ptr if want_out else null
     if inputtype == "wpt":
         fn = getattr(_lib.lib(), "wx_denoise_wpt1d_trees" + xa.suffix)
@@ -250,7 +285,9 @@ _RED_HOST = "a tree matrix (one tree per signal) on a redundant packet table nee
 
 def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batched):
     """denoise / denoiseall(x, :wpt | :swpd | :acwpd, wt; tree = M) with M an (n - 1, N) matrix: signal i in the basis of column i
-    (csrc/wx_denoise_trees.hip; from a redundant packet table, a device tensor, csrc/wx_denoise_red_trees.hip)"""
+    (csrc/wx_denoise_trees.hip; from a redundant packet table, a device tensor, csrc/wx_denoise_red_trees.hip).  estnoise =
+    relerrorthreshold | surethreshold on a redundant table: every signal's threshold over the leaf columns of its own tree
+    (csrc/wx_shrink_trees.hip), for a device table; a table in host memory keeps its refusal"""
     if inputtype not in ("wpt", "swpd", "acwpd"):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs inputtype = :wpt, :swpd or :acwpd")
     red = inputtype != "wpt"
@@ -260,11 +297,17 @@ def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batc
     if estnoise is None or estnoise is noisest:
         thr = None
     elif estnoise is relerrorthreshold or estnoise is surethreshold:
+        kind = 1 if estnoise is relerrorthreshold else 0
         if red:
-            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant table: the selections "
-                                                     "have no per-signal leaf masks")
-        # all coefficients of a non-redundant signal, whatever its tree (Denoising.jl:150-157, 293-300)
-        thr = _select(xa, batched, False, None, 1 if estnoise is relerrorthreshold else 0)
+            if xa.kind != "torch":
+                raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant table in host memory: "
+                                                         "the per-signal leaf masks are built for a device table only")
+            # the leaf columns of every signal's own tree (Denoising.jl:150-157, 293-300), elbows = 2: estnoise(x, true, tree); the N values
+            # stay on the device
+            thr = _select_trees(xa if batched else Arg(xa.arr[..., None]), trees, kind)
+        else:
+            # all coefficients of a non-redundant signal, whatever its tree (Denoising.jl:150-157, 293-300)
+            thr = _select(xa, batched, False, None, kind)
     elif callable(estnoise):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED,
                            "noise estimates on the device path: noisest, relerrorthreshold, surethreshold or precomputed values")
@@ -275,6 +318,8 @@ def _denoise_trees(xa, inputtype, wt, trees, dnt, estnoise, bestTH, smooth, batc
     if bestTH is not None:                                             # one summary threshold for the batch, Denoising.jl:697-700
         if thr is None:
             thr = to_numpy(_trees_call(xa, N, None, trees, dnt.th.kind, dnt.t, None, smooth, False, True, inputtype)[1].arr)
+        elif isinstance(thr, Arg):
+            thr = to_numpy(thr.arr)
         thr = np.full(1, bestTH(np.asarray(thr, dtype=np.float64)), dtype=xa.dtype)
     return _trees_call(xa, N, wt, trees, dnt.th.kind, dnt.t, thr, smooth, True, False, inputtype)[0].arr
 
@@ -293,25 +338,77 @@ def _red_sig_call(xa, wt, trees, L, transform, th_kind, scale, thr, smooth, want
     tb, tp, nt = trees_arg(trees, N, xa)
     out = xa.new((n, N)) if want_out else None
     sig = xa.new((N,)) if want_sigma else None
-    tv = None if thr is None else np.ascontiguousarray(np.atleast_1d(np.asarray(thr, dtype=xa.dtype)))
+    tv, tvp, tvn = _thr_arg(thr, xa.dtype)
     name = ("wx_denoise_swpd1d_sig_trees" if transform == "swpd" else "wx_denoise_acwpd1d_sig_trees") + xa.suffix
     fn = getattr(_lib.lib(), name, None)
     if fn is None:
         raise _lib.WxError(_lib.WX_EUNSUPPORTED, "the autocorrelation transforms are Float64 only")
     _lib.check(fn(xa.ptr, out.ptr if want_out else null, n, L, tp, nt, N, qp, F, int(th_kind), float(scale),
-                  null if tv is None else ctypes.c_void_p(tv.ctypes.data), 0 if tv is None else tv.size,
-                  1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream()))
+                  tvp, tvn, 1 if smooth == "undersmooth" else 0, sig.ptr if want_sigma else null, xa.stream()))
     return out, sig
 
 
-def _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, transform):
+# the packet table of one chunk of signals in _red_chunks: the budget of route 2 of the from-the-signals entries
+_RED_SELECT_BUDGET = 256 << 20
+
+
+def _red_chunks(xa, wt, trees, L, transform, budget=None):
+    """device signals (n, N) by chunks through swpdall / acwpdall(x, wt, L): (b0, b1, the chunk's packet table as an Arg, the chunk's columns
+    of `trees`), a table of at most `budget` bytes (one signal's table where that is larger)"""
+    from .swt import swpdall
+    from .acwt import acwpdall
+    if transform not in ("swpd", "acwpd"):
+        raise ValueError("transform: \"swpd\" or \"acwpd\"")
+    if xa.arr.ndim != 2:
+        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "a tree matrix (one tree per signal) needs 1-D signals, (n, N)")
+    n, N = xa.shape
+    L = maxtransformlevels(n) if L is None else int(L)
+    tr = trees if is_torch(trees) else np.asarray(trees)
+    assert tr.ndim == 2 and N == tr.shape[1]                           # Utils.jl:210
+    budget = _RED_SELECT_BUDGET if budget is None else int(budget)
+    per = max(1, budget // (n * ((2 << L) - 1) * xa.dtype.itemsize))
+    for b0 in range(0, N, per):
+        b1 = min(N, b0 + per)
+        yield b0, b1, Arg((swpdall if transform == "swpd" else acwpdall)(xa.arr[:, b0:b1], wt, L)), tr[:, b0:b1]
+
+
+def _red_select(xa, wt, trees, L, transform, kind, budget=None):
+    """surethreshold (kind 0) / relerrorthreshold (kind 1) of device signals (n, N), each over the leaves of its own tree in swpdall /
+    acwpdall(x, wt, L), chunk by chunk through _select_trees; an Arg with the N thresholds on the device"""
+    out = xa.new((xa.shape[-1],))
+    for b0, b1, table, tr in _red_chunks(xa, wt, trees, L, transform, budget):
+        out.arr[b0:b1] = _select_trees(table, tr, kind).arr
+    return out
+
+
+def _red_denoise_selected(xa, wt, trees, L, dnt, kind, bestTH, smooth, transform, budget=None):
+    """swpd_denoiseall / acwpd_denoiseall with estnoise = surethreshold (kind 0) / relerrorthreshold (kind 1) on device signals: the
+    selections rank whole leaf columns, so a chunk's packet table has to exist; once it does, the chunk is denoised from it
+    (_trees_call, the entries of denoiseall on a table) instead of being transformed a second time by the from-the-signals entry.  The
+    result is therefore the table way's, byte for byte.  bestTH wants every threshold before the first signal is denoised: then the
+    chunks are transformed twice."""
+    n, N = xa.shape[0], xa.shape[-1]
+    one = None
+    if bestTH is not None:                                             # one summary threshold for the batch, Denoising.jl:697-700
+        thr = to_numpy(_red_select(xa, wt, trees, L, transform, kind, budget).arr)
+        one = np.full(1, bestTH(np.asarray(thr, dtype=np.float64)), dtype=xa.dtype)
+    out = xa.new((n, N))
+    for b0, b1, table, tr in _red_chunks(xa, wt, trees, L, transform, budget):
+        thr = one if one is not None else _select_trees(table, tr, kind)
+        out.arr[:, b0:b1] = _trees_call(table, b1 - b0, wt, tr, dnt.th.kind, dnt.t, thr, smooth, True, False, transform)[0].arr
+    return out.arr
+
+
+def _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, transform, select_budget=None):
     xa = Arg(x)
     dnt = VisuShrink(xa.shape[0]) if dnt is None else dnt
     if estnoise is None or estnoise is noisest:
         thr = None
     elif estnoise is relerrorthreshold or estnoise is surethreshold:
-        raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant basis: the selections "
-                                                 "have no per-signal leaf masks")
+        if xa.kind != "torch":
+            raise _lib.WxError(_lib.WX_EUNSUPPORTED, "relerrorthreshold / surethreshold with a tree matrix on a redundant basis of signals in host "
+                                                     "memory: the per-signal leaf masks are built for device signals only")
+        return _red_denoise_selected(xa, wt, trees, L, dnt, 1 if estnoise is relerrorthreshold else 0, bestTH, smooth, transform, select_budget)
     elif callable(estnoise):
         raise _lib.WxError(_lib.WX_EUNSUPPORTED,
                            "noise estimates on the device path: noisest, relerrorthreshold, surethreshold or precomputed values")
@@ -328,7 +425,10 @@ def swpd_denoiseall(x, wt, trees, L=None, dnt=None, estnoise=None, bestTH=None, 
     """denoiseall(swpdall(x, wt, L), "swpd", wt, tree=trees, ...) straight from the signals x (n, N), host or device, with the tree of
     signal i in column i of `trees` ((n - 1, N), host or device: what swpd_bestbasistreeall returns): the (n, 2^(L+1)-1, N) packet table
     is never written (csrc/wx_denoise_red_sig.hip).  No tree may decompose a node of depth >= L (IndexError).  dnt, estnoise (None /
-    noisest / numbers), bestTH and smooth as denoiseall with a tree matrix."""
+    noisest / numbers), bestTH and smooth as denoiseall with a tree matrix.  estnoise = relerrorthreshold | surethreshold, for device
+    signals only: the selections rank whole leaf columns, so chunks of the signals go through packet tables of at most 256 MiB; each
+    chunk's thresholds are selected over the leaves of every signal's own tree (csrc/wx_shrink_trees.hip), stay on the device, and the
+    chunk is denoised from the table it already has: byte for byte denoiseall on the table.  Signals in host memory are refused."""
     return _red_denoiseall(x, wt, trees, L, dnt, estnoise, bestTH, smooth, "swpd")
 
 

@@ -997,6 +997,25 @@ function relerrorthresholdall(coef::HIP{T}, redundant::Bool = false, tree::Union
     check(wx_relerrorthreshold(T, raw(coef), n, k, N, colmask(redundant ? tree : nothing, k), elbows, t, stream()))
     return t
 end
+# one tree per signal (column i of `trees` for signal i) on a redundant packet table (n, ncols, N): every threshold over the leaf columns of
+# its own tree, coef[:, getleaf(treeᵢ), i] (Denoising.jl:150-157, 293-300), in one call (wx_surethreshold_trees_* / wx_relerrorthreshold_trees_*)
+function surethresholdall(coef::HIP{T,3}, redundant::Bool, trees::BitMatrix) where T<:FT
+    redundant || return surethresholdall(coef, false, nothing)             # all coefficients, whatever the tree
+    n, k, N = size(coef)
+    @assert size(trees, 2) == N
+    t = Vector{T}(undef, N); tb = Matrix{UInt8}(trees)
+    check(wx_surethreshold_trees(T, raw(coef), n, k, tb, size(tb, 1), N, t, stream()))
+    return t
+end
+function relerrorthresholdall(coef::HIP{T,3}, redundant::Bool, trees::BitMatrix, elbows::Integer = 2) where T<:FT
+    redundant || return relerrorthresholdall(coef, false, nothing, elbows)
+    @assert elbows ≥ 1
+    n, k, N = size(coef)
+    @assert size(trees, 2) == N
+    t = Vector{T}(undef, N); tb = Matrix{UInt8}(trees)
+    check(wx_relerrorthreshold_trees(T, raw(coef), n, k, tb, size(tb, 1), N, elbows, t, stream()))
+    return t
+end
 surethreshold(coef::HIP{T}, redundant::Bool, tree::Union{BitVector,Nothing} = nothing) where T<:FT =
     surethresholdall(coef, redundant, tree; batched = false)[1]
 relerrorthreshold(coef::HIP{T}, redundant::Bool = false, tree::Union{BitVector,Nothing} = nothing, elbows::Integer = 2) where T<:FT =
@@ -1038,14 +1057,23 @@ function WaveletsExt.Denoising.denoiseall(x::HIP{T,2}, inputtype::Symbol, wt::Or
 end
 
 # denoiseall(xw, :swpd | :acwpd, wt; tree::BitMatrix, ...): every signal denoised from its redundant packet table in its own basis (what
-# bestbasistreeall(xw, BB(redundant = true)) returns) by one launch (denoiseall_red_trees above); wt = nothing with :swpd returns x̃
+# bestbasistreeall(xw, BB(redundant = true)) returns) by one launch (denoiseall_red_trees above); wt = nothing with :swpd returns x̃;
+# estnoise = relerrorthreshold | surethreshold selects every signal's threshold first (surethresholdall / relerrorthresholdall above)
 function WaveletsExt.Denoising.denoiseall(x::HIP{T,3}, inputtype::Symbol, wt::Union{OrthoFilter,Nothing};
         tree::BitMatrix, dnt = VisuShrink(size(x, 1)), estnoise::Union{Function,Vector{<:Number}} = noisest,
         bestTH::Union{Function,Nothing} = nothing, smooth::Symbol = :regular) where T<:FT
     @assert smooth in (:undersmooth, :regular)
     inputtype in (:swpd, :acwpd) || throw(ArgumentError("a packet table with a tree matrix (one tree per signal) needs inputtype = :swpd or :acwpd"))
-    estnoise isa Function && estnoise !== noisest && throw(ArgumentError("device pipeline: estnoise = noisest or precomputed values"))
-    σ = estnoise isa Function ? (bestTH === nothing ? nothing : noisestall(x, true, tree)) : Vector{T}(estnoise)
+    estnoise isa Function && !(estnoise in (noisest, relerrorthreshold, surethreshold)) &&
+        throw(ArgumentError("device pipeline: estnoise = noisest, relerrorthreshold, surethreshold or precomputed values"))
+    # σᵢ = estnoise(xᵢ, true, treeᵢ) (Denoising.jl:687-690): the two selections over the leaves of every signal's own tree, elbows = 2
+    σ = if estnoise === relerrorthreshold
+        relerrorthresholdall(x, true, tree)
+    elseif estnoise === surethreshold
+        surethresholdall(x, true, tree)
+    else
+        estnoise isa Function ? (bestTH === nothing ? nothing : noisestall(x, true, tree)) : Vector{T}(estnoise)
+    end
     bestTH === nothing || (σ = T[bestTH(σ)])                                # summary threshold (Denoising.jl:697-700)
     return denoiseall_red_trees(x, inputtype, wt, tree, dnt.th, dnt.t, smooth === :undersmooth; thr = σ)
 end
